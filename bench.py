@@ -16,7 +16,10 @@ second over the whole job = gpus * batch * steps / wall (max over ranks).  Ranks
 (weak scaling, no data-path collective; the only exchange of the real sampler is the final all-gather of decoded
 frames, outside the step loop).
 
-Two extra objects on the JSON line:
+A plain run sets up, warms up, times the `--steps` steps and prints the line; `--dump-outputs DIR` also writes the latents the
+last timed step produced (DIR/latents.npy, float32).  `--full` adds everything else the benchmark measures, as extra objects on
+the same line (runs of their own, after the timed steps):
+  ensemble_strong_scaling, small_batch, precision_fp32 / _fp16 / _fp16x2, vae - other batch sizes, operand types and the VAE
   roofline     - the dominant kernel (Conv3d 3x3x3 implicit GEMM: igemm256_kernel<2,8> where pd_igemm's heuristic picks the
                  256x256 tile, else igemm_kernel<128,128,64,2,false,2,...>): algorithmic FLOPs per launch / its average launch
                  duration measured here with HIP events, against the dense bf16 MFMA peak.
@@ -354,6 +357,8 @@ def ensemble_e2e(args, ldm, device, rank, world, local_rank, dist):
         el, ag = float(te[0]), float(te[1])
     if rank == 0:
         assert out.shape == (E, 6, 128, 128, 1) and bool(torch.isfinite(out).all())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, "frames", out)
         print(json.dumps({
             "metric": "ensemble_samples_per_sec", "value": round(E * reps / el, 3), "unit": "samples/s", "n_gpus": world, "steps": reps,
             "warmup": min(args.warmup, 2), "ms_per_step": round(el / reps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
@@ -377,6 +382,21 @@ def lanes_for(batch, args):
     return 2 if batch >= 16 else 1      # round 5 (profiles/r05_r_small_batch_lanes.txt): 8 x 1 / 8 x 2 = 951 / 918 steps/s, 12: 1089 / 1021, 16: 1325 / 1345-1358
 
 
+DUMP_MAX_ELEMS = 15_000_000        # --dump-outputs writes at most 60 MB of float32
+
+
+def dump_outputs(out_dir, name, x):
+    """--dump-outputs: `x` as out_dir/<name>.npy in float32.  Larger than DUMP_MAX_ELEMS: a fixed, seeded sample of its elements (in
+    flat-index order) as out_dir/<name>_sample.npy, the same elements in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = x.detach().float().cpu()
+    if a.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+        a, name = a.reshape(-1)[idx], name + "_sample"
+    np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -392,11 +412,17 @@ def main():
                     help="launcher self-test without GPUs: every rank joins a gloo group, rank 0 prints the world it sees, nothing is timed")
     ap.add_argument("--ensemble", type=int, default=32, help="members of the ONE ensemble timed as the strong-scaling line (BASELINE config 3)")
     ap.add_argument("--small-streams", type=int, default=0, help="lanes for the small-batch / strong-scaling lines (0 = automatic)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the strong-scaling and small-batch lines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the strong-scaling, small-batch, other-precision and VAE lines, the per-kernel "
+                         "roofline / attention-block figures and the CPU baseline (off: the headline line alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's final latents; --ensemble-e2e: the decoded frames) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the strong-scaling, small-batch, other-precision and VAE lines, the "
+                                                                   "two-lane roofline and the pair kernel's phase split")
     ap.add_argument("--ensemble-e2e", action="store_true",
                     help="instead of the step benchmark: time sample_ensemble end to end (BASELINE config 3: ONE context, --ensemble members sharded over "
                          "the ranks, VAE encode, DDIM-50, VAE decode, one all-gather of the decoded frames); reports samples/s and the all-gather time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-fused-ffn", action="store_true")
     ap.add_argument("--no-fused-attn", action="store_true")
     ap.add_argument("--no-pair", action="store_true", help="A/B: the level-0 (attention, FFN) pairs as the two round-3 launches instead of pd_attn_ffn_pair")
@@ -408,6 +434,8 @@ def main():
     ap.add_argument("--splitk-max-tiles", type=int, default=-1, help="A/B: split-K Conv3d only for launches of at most this many 256x256 tiles (0 = off)")
     ap.add_argument("--no-tile256", action="store_true", help="A/B: keep pd_igemm on the 128x128 kernel for the long-K launches")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit(f"bench.py: --steps {args.steps} --warmup {args.warmup}: at least one timed step and no negative warm-up")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -556,37 +584,40 @@ def main():
             el = float(te.item())
         fin = torch.cat([lst["z"] for lst in lanes[0]]) if lanes is not None else (st["z"] if st is not None else zx)
         assert bool(torch.isfinite(fin).all()), "non-finite latents after the timed steps"
-        return el, Sx
+        return el, Sx, fin
 
-    elapsed, S = timed_steps(B, args.streams, args.steps, args.warmup)
+    elapsed, S, fin = timed_steps(B, args.streams, args.steps, args.warmup)
     Bl = B // S
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "latents", fin)
+    del fin
 
     # ---- BASELINE config 3 as written: ONE ensemble of `--ensemble` members sharded over the GPUs (strong scaling: global work fixed,
     #      per-GPU sub-batch = ensemble / n_gpus), and the small per-GPU batches it implies, reported beside the headline ----
     strong = None
     small = {}
-    if not args.no_extra and not args.no_graph and args.config == "v1":
+    if args.full and not args.no_extra and not args.no_graph and args.config == "v1":
         E = args.ensemble
         k_extra = min(args.steps, 20)
         if E % world == 0 and E // world <= B:
             Be = E // world
-            el, Se = timed_steps(Be, lanes_for(Be, args), k_extra, 3)
+            el, Se, _ = timed_steps(Be, lanes_for(Be, args), k_extra, 3)
             strong = {"metric": "denoising_steps_per_sec", "ensemble": E, "trajectories_per_gpu": Be, "lanes": Se, "scaling": "strong",
                       "value": round(E * k_extra / el, 2), "unit": "steps/s", "steps": k_extra, "ms_per_step": round(el / k_extra * 1e3, 4)}
         if world == 1:
             for Bs in (1, 4, 16):
                 if Bs <= B:
-                    el, Ss = timed_steps(Bs, lanes_for(Bs, args), k_extra, 3)
+                    el, Ss, _ = timed_steps(Bs, lanes_for(Bs, args), k_extra, 3)
                     small[f"B{Bs}"] = {"value": round(Bs * k_extra / el, 2), "unit": "steps/s", "lanes": Ss, "ms_per_step": round(el / k_extra * 1e3, 4)}
 
     # ---- the fp32-class engine (hi/lo split operands, 3 MFMAs per product: the form the <= 1e-3 parity claim is pinned with) at the
     #      headline configuration: its throughput beside the bf16 headline ----
     fp32_line = None
-    if not args.no_extra and not args.no_graph and args.config == "v1" and args.precision == "bf16" and world == 1:
+    if args.full and not args.no_extra and not args.no_graph and args.config == "v1" and args.precision == "bf16" and world == 1:
         ldm_bf16 = ldm
         ldm = v1_model("fp32", device, args.config)
         k32 = min(args.steps, 8)
-        el32, S32 = timed_steps(B, args.streams, k32, 2)
+        el32, S32, _ = timed_steps(B, args.streams, k32, 2)
         fp32_line = {"value": round(B * k32 / el32, 2), "unit": "steps/s", "dtype": "bf16x3 (hi/lo split operands, fp32-class accuracy)",
                      "steps": k32, "ms_per_step": round(el32 / k32 * 1e3, 4), "trajectories_per_gpu": B, "lanes": S32,
                      "parity": "v1 DDIM-50 vs the oracle loop 1.4e-5 rel-L2 (tests/test_hip_configs.py::test_v1_ddim50_vs_oracle)"}
@@ -597,11 +628,11 @@ def main():
     # ---- the same engine on IEEE-half operands (precision="fp16": 11-bit significands at the bf16 MFMA rate -- the TF32 class of the
     #      reference's own GPU setting): full timed region of the headline configuration ----
     fp16_line = None
-    if not args.no_extra and not args.no_graph and args.config == "v1" and args.precision == "bf16" and world == 1:
+    if args.full and not args.no_extra and not args.no_graph and args.config == "v1" and args.precision == "bf16" and world == 1:
         ldm_bf16 = ldm
         ldm = v1_model("fp16", device, args.config)
         k16 = min(args.steps, 20)
-        el16, S16 = timed_steps(B, args.streams, k16, 3)
+        el16, S16, _ = timed_steps(B, args.streams, k16, 3)
         fp16_line = {"value": round(B * k16 / el16, 2), "unit": "steps/s", "dtype": "fp16 operands, fp32 accumulate (TF32-class accuracy)",
                      "steps": k16, "ms_per_step": round(el16 / k16 * 1e3, 4), "trajectories_per_gpu": B, "lanes": S16,
                      "parity": "v1 DDIM-50 vs the oracle loop: tests/test_hip_configs.py::test_v1_ddim50_vs_oracle prints it beside the other modes"}
@@ -612,7 +643,7 @@ def main():
     # ---- precision="fp16x2": IEEE-half activations x (hi + lo) IEEE-half weights, two MFMA products per k-step -- the engine that holds the
     #      north-star 1e-3 bar over DDIM-50 with a single-pass activation path (round 6) ----
     fp16x2_line = None
-    if not args.no_extra and not args.no_graph and args.config == "v1" and args.precision == "bf16" and world == 1:
+    if args.full and not args.no_extra and not args.no_graph and args.config == "v1" and args.precision == "bf16" and world == 1:
         # each in its own process (this script with --precision ... --no-extra): what a user's process running that engine gets, with nothing of
         # the other engines' graphs and workspaces around
         import subprocess
@@ -640,20 +671,6 @@ def main():
     if rank == 0:
         n_gpus = world
         value = n_gpus * B * args.steps / elapsed
-        ldm.num_streams = S
-        ker_s, launches, attn_s, attn_launches, pair_s, pair_launches, pair512_s, pair512_launches = kernel_times(ldm, Bl, device, cond_shape=WL["cond"])     # the kernels as launched: one lane's sub-batch
-        flops_per_launch = WL["conv3d_gflop"] * 1e9 * Bl / CONV3D_LAUNCHES_PER_STEP
-        achieved = flops_per_launch / ker_s / 1e12
-        traffic = None
-        tp = os.path.join(ROOT, "profiles", "conv3d_hbm_traffic.json")
-        if os.path.exists(tp) and args.config == "v1" and args.precision in ("bf16", "fp8", "fp8_conv"):
-            try:
-                traffic = json.load(open(tp)).get(f"B{Bl}" + ("" if args.precision == "bf16" else "_fp8"))
-            except Exception:
-                traffic = None
-        # --precision fp8 / fp8_conv: the Conv3d launches (the dominant kernel) run on e4m3 operands and are priced against the fp8 peak; every other
-        # GEMM of the step stays bf16
-        conv_peak = PEAK_FP8_TFLOPS if args.precision.startswith("fp8") else PEAK_BF16_TFLOPS
         line = {
             "metric": "denoising_steps_per_sec", "value": round(value, 2), "unit": "steps/s", "n_gpus": n_gpus,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -670,118 +687,133 @@ def main():
                        "parallelism": f"ensemble-shard x{n_gpus}"},
             "step_tflops": round(WL["unet_gflop"] * 1e9 * value / n_gpus / 1e12, 2),
             "step_frac_of_bf16_peak": round(WL["unet_gflop"] * 1e9 * value / n_gpus / 1e12 / PEAK_BF16_TFLOPS, 4),
-            "roofline": {"bound": "mfma", "kernel": CONV3D_KERNEL_LABEL,
-                         "achieved": round(achieved, 2), "peak": conv_peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / conv_peak, 4), "traffic": traffic,
-                         "traffic_source": "profiles/conv3d_hbm_traffic.json: (2*FETCH_SIZE + WRITE_SIZE) KiB per launch from separate "
-                                           "rocprofv3 --pmc passes of this kernel (scripts/pmc_bench.sh); not re-measured inside this run",
-                         "avg_launch_us": round(ker_s * 1e6, 2), "launches_per_step": launches * S,
-                         "gflop_per_launch": round(flops_per_launch / 1e9, 3)},
         }
-        if S == 2 and args.config == "v1" and not args.no_extra:
-            # the same kernel as it runs in the timed configuration: both lanes active
-            ldm_b = v1_model(args.precision, device, args.config)
-            ker2_s, n2 = kernel_times_two_lanes(ldm, ldm_b, Bl, device, cond_shape=WL["cond"])
-            del ldm_b
-            ach2 = flops_per_launch / ker2_s / 1e12
-            line["roofline"]["in_situ"] = {"what": "average launch duration with both lanes active (two streams, HIP events per launch)",
-                                           "avg_launch_us": round(ker2_s * 1e6, 2), "achieved": round(ach2, 2),
-                                           "frac": round(ach2 / conv_peak, 4), "launches_timed": n2}
-        if (attn_s or pair_s) and args.config == "v1":
-            # level-0 block: LN -> QKV (2*S*3C*C) -> core (4*S*vol*C) -> proj (2*S*C*C), S = 3328 tokens, C = 256, vol 13 or 16;
-            # its FFN: 2 * 2*S*C*4C.  
-            gf_attn = Bl * (2 * 3328 * 768 * 256 + 2 * 3328 * 256 * 256 + 4 * 3328 * 15 * 256) / 1e9
-            gf_ffn = Bl * (2 * 2 * 3328 * 256 * 1024) / 1e9
-            attn_alone = None
-            if attn_s:
-                attn_alone = {"kernel": "attn_block_kernel<256> (LN -> QKV -> cuboid attention -> proj -> +x, level 0; the round-3 kernel, "
-                                        "measured with the pair kernel switched off)" if pair_s else
-                                        "attn_block_kernel<256> (LN -> QKV -> cuboid attention -> proj -> +x, level 0)",
-                              "achieved": round(gf_attn / attn_s / 1e3, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                              "frac": round(gf_attn / attn_s / 1e3 / PEAK_BF16_TFLOPS, 4), "avg_launch_us": round(attn_s * 1e6, 2),
-                              "launches_per_step": attn_launches * S, "gflop_per_launch": round(gf_attn, 3)}
-            if pair_s:
-                gf = gf_attn + gf_ffn
-                line["attention_block"] = {
-                    "kernel": "pair_kernel (csrc/pair_block.hip): LN -> QKV -> cuboid attention -> proj -> +x -> LN -> FFN-1 -> GELU -> FFN-2 -> +x "
-                              "of one level-0 (attention, FFN) pair in ONE launch, rows register resident",
-                    "achieved": round(gf / pair_s / 1e3, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(gf / pair_s / 1e3 / PEAK_BF16_TFLOPS, 4), "avg_launch_us": round(pair_s * 1e6, 2),
-                    "launches_per_step": pair_launches * S, "gflop_per_launch": round(gf, 3),
-                    "gflop_attention_part": round(gf_attn, 3), "gflop_ffn_part": round(gf_ffn, 3),
-                    "attention_block_alone_round3_kernel": attn_alone}
-            else:
-                line["attention_block"] = attn_alone
-            if pair512_s:
-                # level-1 pair: S = 832 tokens, C = 512, hidden 2048, cuboid volume 13 or 8
-                gf1 = Bl * 832 * (2 * 4 * 512 * 512 + 2 * 2 * 512 * 2048 + 4 * 10 * 512) / 1e9
-                line["attention_block_level1"] = {
-                    "kernel": "pair_kernel<1, 2> (csrc/pair_block.hip): the same pair at units 512 (4 heads of 128, hidden 2048), 16 rows per wave; "
-                              "replaces qkv / proj / FFN-1 / FFN-2 GEMM launches + 2 LayerNorm + attention core launches",
-                    "achieved": round(gf1 / pair512_s / 1e3, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(gf1 / pair512_s / 1e3 / PEAK_BF16_TFLOPS, 4), "avg_launch_us": round(pair512_s * 1e6, 2),
-                    "launches_per_step": pair512_launches * S, "gflop_per_launch": round(gf1, 3)}
-        if pair_s and args.config == "v1" and not args.no_extra and n_gpus == 1 and args.precision in ("bf16", "fp16"):
-            ph = pair_phases(Bl, args.precision)
-            if ph is not None:
-                for key, units in (("attention_block", 256), ("attention_block_level1", 512)):
-                    rows = [r for r in ph["layers"] if r["units"] == units]
-                    if key in line and rows:
-                        mean = lambda k: sum(r[k] for r in rows) / len(rows)
-                        sh_a, sh_f = mean("attention_share"), mean("ffn_share")
-                        # FLOPs of the two phases per launch over their share of THIS run's launch time
-                        if units == 256:
-                            gfa, gff = line[key]["gflop_attention_part"], line[key]["gflop_ffn_part"]
-                        else:
-                            gfa = Bl * 832 * (2 * 4 * 512 * 512 + 4 * 10 * 512) / 1e9
-                            gff = Bl * 832 * (2 * 2 * 512 * 2048) / 1e9
-                        us = line[key]["avg_launch_us"]
-                        tb_us = mean("launch_us")
-                        pr_us = mean("product_launch_us") if all("product_launch_us" in r for r in rows) else us
-                        if abs(tb_us / pr_us - 1.0) > 0.10:
-                            # the stamps are evidence for the product kernel only if the traced build runs like it (the old 24-stamp
-                            # build of the units-512 form ran 3x slower): say so instead of printing shares of a different kernel
-                            line[key]["phases"] = {"dropped": "trace build launch differs from the product launch by more than 10 %",
-                                                   "trace_build_launch_us": round(tb_us, 1), "product_launch_us_same_microbench": round(pr_us, 1)}
-                            continue
-                        line[key]["phases"] = {
-                            "what": "the launch split by the kernel's own clock stamps (three per tile, held in scalar registers: the -DPD_PAIR_TRACE=1 build "
-                                    "of the same source, scripts/bench_pair.py phases, mean over the three axial layers; applied to this run's launch time): "
-                                    "attention = LayerNorm-1 .. proj + residual, ffn = LayerNorm-2 .. FFN-2 + residual",
-                            "attention_share_of_launch": round(sh_a, 4), "ffn_share_of_launch": round(sh_f, 4),
-                            "attention_us": round(sh_a * us, 2), "ffn_us": round(sh_f * us, 2),
-                            "attention_gflop": round(gfa, 3), "ffn_gflop": round(gff, 3),
-                            "attention_frac_of_peak": round(gfa / (sh_a * us) * 1e3 / PEAK_BF16_TFLOPS, 4),
-                            "ffn_frac_of_peak": round(gff / (sh_f * us) * 1e3 / PEAK_BF16_TFLOPS, 4),
-                            "trace_build_launch_us": round(tb_us, 1), "product_launch_us_same_microbench": round(pr_us, 1),
-                            "trace_build_vs_product": round(tb_us / pr_us, 3)}
-        if strong is not None:
-            if n_gpus == 1 and "B4" in small and strong["ensemble"] == 32:
-                # what the SAME ensemble would do on 8 GPUs (4 members each): the step loop has no collective, so 8 x the measured
-                # 4-trajectory rate -- a projection from this GPU's own numbers, not a measurement
-                strong["projected_8gpu"] = {"trajectories_per_gpu": 4, "steps_per_sec": round(8 * small["B4"]["value"], 1),
-                                            "speedup_vs_this_gpu": round(8 * small["B4"]["value"] / strong["value"], 2),
-                                            "basis": "8 x small_batch.B4 (no collective in the step loop); north-star target 6x",
-                                            # the arithmetic of the 6x target: what 4 trajectories per GPU would have to
-                                            # run at, and what they would run at if every kernel kept the per-trajectory cost it has at
-                                            # full occupancy (this run's headline rate) -- the ceiling of any small-batch engine
-                                            "needed_B4_steps_per_sec_for_6x": round(6.0 * strong["value"] / 8.0, 1),
-                                            "B4_at_full_occupancy_kernel_efficiency": round(value, 1),
-                                            "speedup_ceiling_at_that_efficiency": round(8.0 * value / strong["value"], 2),
-                                            "B4_fraction_of_that_ceiling": round(small["B4"]["value"] / value, 3)}
-            line["ensemble_strong_scaling"] = strong      # BASELINE configs[2]: ensemble=32 over the node's GPUs
-        if small:
-            line["small_batch"] = small                   # B in {1..16} beside the headline batch
-        if fp32_line is not None:
-            line["precision_fp32"] = fp32_line
-        if fp16_line is not None:
-            line["precision_fp16"] = fp16_line
-        if fp16x2_line is not None:
-            line["precision_fp16x2"] = fp16x2_line
-        if not args.no_extra and args.config == "v1" and n_gpus == 1:
-            line["vae"] = vae_times(device, trajectories=min(B, 32))
-        if not args.no_cpu_baseline and n_gpus == 1 and args.config == "v1":
-            line["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            ldm.num_streams = S
+            ker_s, launches, attn_s, attn_launches, pair_s, pair_launches, pair512_s, pair512_launches = kernel_times(ldm, Bl, device, cond_shape=WL["cond"])     # the kernels as launched: one lane's sub-batch
+            flops_per_launch = WL["conv3d_gflop"] * 1e9 * Bl / CONV3D_LAUNCHES_PER_STEP
+            achieved = flops_per_launch / ker_s / 1e12
+            traffic = None
+            tp = os.path.join(ROOT, "profiles", "conv3d_hbm_traffic.json")
+            if os.path.exists(tp) and args.config == "v1" and args.precision in ("bf16", "fp8", "fp8_conv"):
+                try:
+                    traffic = json.load(open(tp)).get(f"B{Bl}" + ("" if args.precision == "bf16" else "_fp8"))
+                except Exception:
+                    traffic = None
+            # --precision fp8 / fp8_conv: the Conv3d launches (the dominant kernel) run on e4m3 operands and are priced against the fp8 peak; every other
+            # GEMM of the step stays bf16
+            conv_peak = PEAK_FP8_TFLOPS if args.precision.startswith("fp8") else PEAK_BF16_TFLOPS
+            line["roofline"] = {"bound": "mfma", "kernel": CONV3D_KERNEL_LABEL,
+                                "achieved": round(achieved, 2), "peak": conv_peak, "unit": "TFLOP/s",
+                                "frac": round(achieved / conv_peak, 4), "traffic": traffic,
+                                "traffic_source": "profiles/conv3d_hbm_traffic.json: (2*FETCH_SIZE + WRITE_SIZE) KiB per launch from separate "
+                                                  "rocprofv3 --pmc passes of this kernel (scripts/pmc_bench.sh); not re-measured inside this run",
+                                "avg_launch_us": round(ker_s * 1e6, 2), "launches_per_step": launches * S,
+                                "gflop_per_launch": round(flops_per_launch / 1e9, 3)}
+            if S == 2 and args.config == "v1" and not args.no_extra:
+                # the same kernel as it runs in the timed configuration: both lanes active
+                ldm_b = v1_model(args.precision, device, args.config)
+                ker2_s, n2 = kernel_times_two_lanes(ldm, ldm_b, Bl, device, cond_shape=WL["cond"])
+                del ldm_b
+                ach2 = flops_per_launch / ker2_s / 1e12
+                line["roofline"]["in_situ"] = {"what": "average launch duration with both lanes active (two streams, HIP events per launch)",
+                                               "avg_launch_us": round(ker2_s * 1e6, 2), "achieved": round(ach2, 2),
+                                               "frac": round(ach2 / conv_peak, 4), "launches_timed": n2}
+            if (attn_s or pair_s) and args.config == "v1":
+                # level-0 block: LN -> QKV (2*S*3C*C) -> core (4*S*vol*C) -> proj (2*S*C*C), S = 3328 tokens, C = 256, vol 13 or 16;
+                # its FFN: 2 * 2*S*C*4C.  
+                gf_attn = Bl * (2 * 3328 * 768 * 256 + 2 * 3328 * 256 * 256 + 4 * 3328 * 15 * 256) / 1e9
+                gf_ffn = Bl * (2 * 2 * 3328 * 256 * 1024) / 1e9
+                attn_alone = None
+                if attn_s:
+                    attn_alone = {"kernel": "attn_block_kernel<256> (LN -> QKV -> cuboid attention -> proj -> +x, level 0; the round-3 kernel, "
+                                            "measured with the pair kernel switched off)" if pair_s else
+                                            "attn_block_kernel<256> (LN -> QKV -> cuboid attention -> proj -> +x, level 0)",
+                                  "achieved": round(gf_attn / attn_s / 1e3, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                                  "frac": round(gf_attn / attn_s / 1e3 / PEAK_BF16_TFLOPS, 4), "avg_launch_us": round(attn_s * 1e6, 2),
+                                  "launches_per_step": attn_launches * S, "gflop_per_launch": round(gf_attn, 3)}
+                if pair_s:
+                    gf = gf_attn + gf_ffn
+                    line["attention_block"] = {
+                        "kernel": "pair_kernel (csrc/pair_block.hip): LN -> QKV -> cuboid attention -> proj -> +x -> LN -> FFN-1 -> GELU -> FFN-2 -> +x "
+                                  "of one level-0 (attention, FFN) pair in ONE launch, rows register resident",
+                        "achieved": round(gf / pair_s / 1e3, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(gf / pair_s / 1e3 / PEAK_BF16_TFLOPS, 4), "avg_launch_us": round(pair_s * 1e6, 2),
+                        "launches_per_step": pair_launches * S, "gflop_per_launch": round(gf, 3),
+                        "gflop_attention_part": round(gf_attn, 3), "gflop_ffn_part": round(gf_ffn, 3),
+                        "attention_block_alone_round3_kernel": attn_alone}
+                else:
+                    line["attention_block"] = attn_alone
+                if pair512_s:
+                    # level-1 pair: S = 832 tokens, C = 512, hidden 2048, cuboid volume 13 or 8
+                    gf1 = Bl * 832 * (2 * 4 * 512 * 512 + 2 * 2 * 512 * 2048 + 4 * 10 * 512) / 1e9
+                    line["attention_block_level1"] = {
+                        "kernel": "pair_kernel<1, 2> (csrc/pair_block.hip): the same pair at units 512 (4 heads of 128, hidden 2048), 16 rows per wave; "
+                                  "replaces qkv / proj / FFN-1 / FFN-2 GEMM launches + 2 LayerNorm + attention core launches",
+                        "achieved": round(gf1 / pair512_s / 1e3, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(gf1 / pair512_s / 1e3 / PEAK_BF16_TFLOPS, 4), "avg_launch_us": round(pair512_s * 1e6, 2),
+                        "launches_per_step": pair512_launches * S, "gflop_per_launch": round(gf1, 3)}
+            if pair_s and args.config == "v1" and not args.no_extra and n_gpus == 1 and args.precision in ("bf16", "fp16"):
+                ph = pair_phases(Bl, args.precision)
+                if ph is not None:
+                    for key, units in (("attention_block", 256), ("attention_block_level1", 512)):
+                        rows = [r for r in ph["layers"] if r["units"] == units]
+                        if key in line and rows:
+                            mean = lambda k: sum(r[k] for r in rows) / len(rows)
+                            sh_a, sh_f = mean("attention_share"), mean("ffn_share")
+                            # FLOPs of the two phases per launch over their share of THIS run's launch time
+                            if units == 256:
+                                gfa, gff = line[key]["gflop_attention_part"], line[key]["gflop_ffn_part"]
+                            else:
+                                gfa = Bl * 832 * (2 * 4 * 512 * 512 + 4 * 10 * 512) / 1e9
+                                gff = Bl * 832 * (2 * 2 * 512 * 2048) / 1e9
+                            us = line[key]["avg_launch_us"]
+                            tb_us = mean("launch_us")
+                            pr_us = mean("product_launch_us") if all("product_launch_us" in r for r in rows) else us
+                            if abs(tb_us / pr_us - 1.0) > 0.10:
+                                # the stamps are evidence for the product kernel only if the traced build runs like it (the old 24-stamp
+                                # build of the units-512 form ran 3x slower): say so instead of printing shares of a different kernel
+                                line[key]["phases"] = {"dropped": "trace build launch differs from the product launch by more than 10 %",
+                                                       "trace_build_launch_us": round(tb_us, 1), "product_launch_us_same_microbench": round(pr_us, 1)}
+                                continue
+                            line[key]["phases"] = {
+                                "what": "the launch split by the kernel's own clock stamps (three per tile, held in scalar registers: the -DPD_PAIR_TRACE=1 build "
+                                        "of the same source, scripts/bench_pair.py phases, mean over the three axial layers; applied to this run's launch time): "
+                                        "attention = LayerNorm-1 .. proj + residual, ffn = LayerNorm-2 .. FFN-2 + residual",
+                                "attention_share_of_launch": round(sh_a, 4), "ffn_share_of_launch": round(sh_f, 4),
+                                "attention_us": round(sh_a * us, 2), "ffn_us": round(sh_f * us, 2),
+                                "attention_gflop": round(gfa, 3), "ffn_gflop": round(gff, 3),
+                                "attention_frac_of_peak": round(gfa / (sh_a * us) * 1e3 / PEAK_BF16_TFLOPS, 4),
+                                "ffn_frac_of_peak": round(gff / (sh_f * us) * 1e3 / PEAK_BF16_TFLOPS, 4),
+                                "trace_build_launch_us": round(tb_us, 1), "product_launch_us_same_microbench": round(pr_us, 1),
+                                "trace_build_vs_product": round(tb_us / pr_us, 3)}
+            if strong is not None:
+                if n_gpus == 1 and "B4" in small and strong["ensemble"] == 32:
+                    # what the SAME ensemble would do on 8 GPUs (4 members each): the step loop has no collective, so 8 x the measured
+                    # 4-trajectory rate -- a projection from this GPU's own numbers, not a measurement
+                    strong["projected_8gpu"] = {"trajectories_per_gpu": 4, "steps_per_sec": round(8 * small["B4"]["value"], 1),
+                                                "speedup_vs_this_gpu": round(8 * small["B4"]["value"] / strong["value"], 2),
+                                                "basis": "8 x small_batch.B4 (no collective in the step loop); north-star target 6x",
+                                                # the arithmetic of the 6x target: what 4 trajectories per GPU would have to
+                                                # run at, and what they would run at if every kernel kept the per-trajectory cost it has at
+                                                # full occupancy (this run's headline rate) -- the ceiling of any small-batch engine
+                                                "needed_B4_steps_per_sec_for_6x": round(6.0 * strong["value"] / 8.0, 1),
+                                                "B4_at_full_occupancy_kernel_efficiency": round(value, 1),
+                                                "speedup_ceiling_at_that_efficiency": round(8.0 * value / strong["value"], 2),
+                                                "B4_fraction_of_that_ceiling": round(small["B4"]["value"] / value, 3)}
+                line["ensemble_strong_scaling"] = strong      # BASELINE configs[2]: ensemble=32 over the node's GPUs
+            if small:
+                line["small_batch"] = small                   # B in {1..16} beside the headline batch
+            if fp32_line is not None:
+                line["precision_fp32"] = fp32_line
+            if fp16_line is not None:
+                line["precision_fp16"] = fp16_line
+            if fp16x2_line is not None:
+                line["precision_fp16x2"] = fp16x2_line
+            if not args.no_extra and args.config == "v1" and n_gpus == 1:
+                line["vae"] = vae_times(device, trajectories=min(B, 32))
+            if not args.no_cpu_baseline and n_gpus == 1 and args.config == "v1":
+                line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier(device_ids=[local_rank])
