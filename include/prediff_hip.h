@@ -268,6 +268,10 @@ int pd_ddpm_step(const float* zt, const float* eps, const float* noise, const fl
 int pd_ddim_step(const float* zt, const float* eps, const float* noise, const float* coef, float* out, int B,
                  int64_t per_sample, pd_stream_t stream);
 
+/* Knowledge-alignment guided DDIM step: out = <pd_ddim_step> - gamma * shift, the subtraction last, so a zero shift
+ *   gives pd_ddim_step's result bit for bit.  coef4 (B,4) fp32 per sample: [a_t, a_prev, sigma, gamma]; shift: fp32 like zt. */
+int pd_ddim_step_guided(const float* zt, const float* eps, const float* noise, const float* shift, const float* coef4, float* out, int B, int64_t per_sample, pd_stream_t stream);
+
 /* Layout glue for the frame-wise VAE: fp32 NCHW <-> channels-last NHWC (taming/autoencoder_kl.py:80-113 callers,
  * latent_diffusion.py:361-380,423-432). */
 int pd_nchw_to_nhwc(const float* x, float* out, int N, int C, int HW, int ld_out, pd_stream_t stream);

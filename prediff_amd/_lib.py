@@ -132,6 +132,7 @@ _PROTOS = {
     "pd_add": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "pd_ddpm_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
     "pd_ddim_step": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_ddim_step_guided": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -405,6 +406,16 @@ def ddpm_step(zt, eps, noise, mean_shift, t, coef, T, out, B, per_sample, temper
 def ddim_step(zt, eps, noise, coef, out, B, per_sample):
     _check(lib().pd_ddim_step(ptr(zt), ptr(eps), ptr(noise), ptr(coef), ptr(out), B, per_sample, stream_ptr()),
            "pd_ddim_step")
+
+
+def ddim_step_guided(zt, eps, noise, shift, coef4, out, B, per_sample):
+    """pd_ddim_step minus gamma * shift (coef4 rows: a_t, a_prev, sigma, gamma); `noise` may be None (eta = 0)."""
+    n = B * per_sample
+    for name, x, need in (("zt", zt, n), ("eps", eps, n), ("noise", noise, n), ("shift", shift, n), ("coef4", coef4, 4 * B), ("out", out, n)):
+        if x is not None and (x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < need):
+            raise PrediffHipError(f"ddim_step_guided: {name} must be a contiguous fp32 tensor of >= {need} elements")
+    _check(lib().pd_ddim_step_guided(ptr(zt), ptr(eps), ptr(noise), ptr(shift), ptr(coef4), ptr(out), B, per_sample, stream_ptr()),
+           "pd_ddim_step_guided")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):

@@ -149,24 +149,43 @@ extern "C" int pd_ddpm_step(const float* zt, const float* eps, const float* nois
 }
 
 // ---- DDIM step (parity-unpinned; see header) ----
+// GUIDED: coefficient rows (a_t, a_prev, sigma, gamma) and the knowledge-alignment shift, subtracted as the very last operation
+// (out - gamma * shift), so a zero shift gives the un-guided result bit for bit.  The shift pointer is a trailing parameter pack
+// (one pointer when GUIDED, none otherwise): the un-guided instantiation has exactly the kernel arguments, and so the kernel-argument
+// offsets and the instruction stream, of the single-mode kernel it replaces.
+template <typename P> __device__ __forceinline__ P first_of(P p) { return p; }
+template <bool GUIDED, typename... Shift>
 __global__ void __launch_bounds__(256) ddim_step_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
                                                         const float* __restrict__ noise, const float* __restrict__ coef,
-                                                        float* __restrict__ out, int64_t per) {
+                                                        float* __restrict__ out, int64_t per, const Shift* __restrict__... shift) {
+  static_assert(sizeof...(Shift) == (GUIDED ? 1 : 0), "the guided step takes one shift pointer, the un-guided none");
+  constexpr int NC = GUIDED ? 4 : 3;
   const int b = blockIdx.y;
-  const float a_t = coef[b * 3], a_prev = coef[b * 3 + 1], sigma = coef[b * 3 + 2];
+  const float a_t = coef[b * NC], a_prev = coef[b * NC + 1], sigma = coef[b * NC + 2];
   const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t), sp = sqrtf(a_prev);
   const float dir = sqrtf(fmaxf(0.f, 1.f - a_prev - sigma * sigma));
   const int64_t base = (int64_t)b * per;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
     const float e = eps[base + i];
     const float z0 = (zt[base + i] - s1 * e) * r;
-    out[base + i] = sp * z0 + dir * e + (noise ? sigma * noise[base + i] : 0.f);
+    float v = sp * z0 + dir * e + (noise ? sigma * noise[base + i] : 0.f);
+    if constexpr (GUIDED) v = v - coef[b * NC + 3] * first_of(shift...)[base + i];
+    out[base + i] = v;
   }
 }
 extern "C" int pd_ddim_step(const float* zt, const float* eps, const float* noise, const float* coef, float* out, int B,
                             int64_t per_sample, pd_stream_t stream) {
   PD_CHECK_ARG(zt && eps && coef && out && B > 0, "pd_ddim_step: bad args");
-  hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, coef, out, per_sample);
+  hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, coef, out,
+                     per_sample);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+extern "C" int pd_ddim_step_guided(const float* zt, const float* eps, const float* noise, const float* shift, const float* coef4, float* out,
+                                   int B, int64_t per_sample, pd_stream_t stream) {
+  PD_CHECK_ARG(zt && eps && shift && coef4 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_ddim_step_guided: bad args");
+  hipLaunchKernelGGL((ddim_step_kernel<true, float>), dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, coef4, out,
+                     per_sample, shift);
   PD_CHECK_LAUNCH();
   return PD_OK;
 }

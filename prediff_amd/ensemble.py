@@ -95,14 +95,15 @@ def sample_ensemble(ldm, cond, num_members: int, base_seed: int = 0, sampler: st
             outs.append(sample_fn(cb, ks))
             continue
         noise = member_noise_fn(latent_shape, ks, base_seed, device)
-        kw = dict(batch_size=len(ks), return_decoded=return_decoded, noise_tape=_LazyTape(noise))
+        ak = None
+        if use_alignment and alignment_kwargs is not None:
+            ak = {k: (v.expand(len(ks), *v.shape[1:]) if torch.is_tensor(v) and v.shape[0] == 1 else v) for k, v in alignment_kwargs.items()}
+        kw = dict(batch_size=len(ks), return_decoded=return_decoded, noise_tape=_LazyTape(noise), use_alignment=use_alignment,
+                  alignment_kwargs=ak)
         if sampler == "ddim":
             out = ldm.sample(cb, sampler="ddim", ddim_steps=ddim_steps, eta=eta, **kw)
         else:
-            ak = None
-            if use_alignment and alignment_kwargs is not None:
-                ak = {k: (v.expand(len(ks), *v.shape[1:]) if torch.is_tensor(v) and v.shape[0] == 1 else v) for k, v in alignment_kwargs.items()}
-            out = ldm.sample(cb, timesteps=timesteps, use_alignment=use_alignment, alignment_kwargs=ak, **kw)
+            out = ldm.sample(cb, timesteps=timesteps, **kw)
         outs.append(out)
     if outs:
         local = torch.cat(outs)

@@ -25,7 +25,8 @@ from . import _lib as L
 from .distributions import DiagonalGaussianDistribution
 from .ema import LitEma
 from .loss_eval import LossEvaluationMixin
-from .schedule import make_beta_schedule, make_ddim_sampling_parameters, make_ddim_timesteps, schedule_tables
+from .schedule import (make_beta_schedule, make_ddim_guidance_coefficients, make_ddim_sampling_parameters, make_ddim_timesteps,
+                       schedule_tables)
 
 
 def parse_layout_shape(layout: str) -> Dict[str, int]:
@@ -482,6 +483,57 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                 if t is not None:
                     t.record_stream(stream)           # the caching allocator must not recycle it before the lane has read it
 
+    def _aligned_eps_lanes(self, B, cond, device):
+        """Denoiser-only ("eps") graphs of a knowledge-aligned loop (ancestral or DDIM): per-lane graph states, streams, lane batch.
+        One denoiser graph on one side stream by default: the guidance is the concurrent second stream of work, and splitting the
+        denoiser into lanes as well only makes the three compete (measured at 32 / 8 trajectories: 33.4 / 11.6 ms per step with one
+        lane, 34.8 / 13.6 with two, 37.2 / 16.0 with four -- profiles/r02_j_time_alignment*.log).  `aligned_lanes` overrides."""
+        eps_lanes = None
+        saved = (self._num_streams, self._lanes_pinned)
+        try:                                 # an exception in the capture must not leave the module with another lane count
+            self.num_streams = max(1, int(self.aligned_lanes))
+            if B % max(1, self.num_streams):
+                self.num_streams = 1
+            eps_lanes = self._lanes("eps", B, cond, device, True) if self.num_streams > 1 else None
+        finally:
+            self._num_streams, self._lanes_pinned = saved
+        if eps_lanes is None:
+            key = str(device)
+            if len(self._lane_streams.get(key, ())) < 1:
+                self._lane_streams[key] = [torch.cuda.Stream(device=device)]
+            eps_lanes = ([self._graph_step("eps", B, cond, device, lane=0)], self._lane_streams[key][:1], B)
+        return eps_lanes
+
+    def _aligned_eps_and_shift(self, eps_lanes, cur, t, ts, cond, y, alignment_kwargs, device):
+        """One knowledge-aligned step's two inputs of the step epilogue: the denoiser graphs of the lanes replayed at (cur, t) on
+        their streams while the guidance gradient (PyTorch autograd) runs on the WHOLE batch -- the avg_x objective couples a batch
+        through one L2 norm -- on the caller's stream or, with `guidance_high_priority`, on a high-priority side stream.
+        Returns (eps, shift), both ready on the caller's stream."""
+        sts, streams, Bl = eps_lanes
+
+        def fill(lst, sl):
+            lst["z"].copy_(cur[sl])
+            lst["t"].fill_(t)
+        self._lane_step(sts, streams, Bl, device, fill, keep=(cur,), advance=False)
+        if self.guidance_high_priority:
+            # the guidance on its own HIGH-priority stream: its many small kernels are dispatched ahead of the denoiser
+            # graph's queued workgroups whenever a CU has room, instead of taking turns with whole kernels
+            main = torch.cuda.current_stream(device)
+            gs = self._guidance_stream(device)
+            gs.wait_stream(main)
+            with torch.cuda.stream(gs):
+                shift = self.alignment_fn(cur, ts, zc=cond, y=y, **(alignment_kwargs or {})).contiguous().float()
+            for tns in (cur, ts):
+                tns.record_stream(gs)
+            main.wait_stream(gs)
+            shift.record_stream(main)
+        else:
+            shift = self.alignment_fn(cur, ts, zc=cond, y=y, **(alignment_kwargs or {})).contiguous().float()
+        for stream in streams:
+            torch.cuda.current_stream(device).wait_stream(stream)
+        eps = sts[0]["out"] if len(sts) == 1 else torch.cat([lst["out"] for lst in sts], dim=0)
+        return eps, shift
+
     # ------------------------------------------------------------------------------------------------ loops
     @torch.no_grad()
     @_on_own_device
@@ -532,22 +584,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         # concurrently with the denoiser graphs of the lanes; the step epilogue joins them.  Same arithmetic as the eager path.
         eps_lanes = None
         if use_alignment and self.use_hip_graph and self.parameterization == "eps" and img.is_cuda and isinstance(cond, torch.Tensor) and not shorten:
-            # one denoiser graph on one side stream: the guidance is the concurrent second stream of work, and splitting the denoiser
-            # into lanes as well only makes the three compete (measured at 32 / 8 trajectories: 33.4 / 11.6 ms per step with one
-            # lane, 34.8 / 13.6 with two, 37.2 / 16.0 with four -- profiles/r02_j_time_alignment*.log).  `aligned_lanes` overrides.
-            saved = (self._num_streams, self._lanes_pinned)
-            try:                                 # an exception in the capture must not leave the module with another lane count
-                self.num_streams = max(1, int(self.aligned_lanes))
-                if B % max(1, self.num_streams):
-                    self.num_streams = 1
-                eps_lanes = self._lanes("eps", B, cond, device, True) if self.num_streams > 1 else None
-            finally:
-                self._num_streams, self._lanes_pinned = saved
-            if eps_lanes is None:
-                key = str(device)
-                if len(self._lane_streams.get(key, ())) < 1:
-                    self._lane_streams[key] = [torch.cuda.Stream(device=device)]
-                eps_lanes = ([self._graph_step("eps", B, cond, device, lane=0)], self._lane_streams[key][:1], B)
+            eps_lanes = self._aligned_eps_lanes(B, cond, device)
         st = self._graph_step("ddpm", B, cond, device) if use_graph else None
         for k, i in enumerate(reversed(range(0, timesteps))):
             if shorten:
@@ -558,31 +595,9 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             else:
                 noise = noise_tape[1 + k].to(device) if noise_tape is not None else None
             if eps_lanes is not None:
-                sts, streams, Bl = eps_lanes
                 ts = torch.full((B,), i, device=device, dtype=torch.long)
                 cur = img
-
-                def fill(lst, sl, i=i, cur=cur):
-                    lst["z"].copy_(cur[sl])
-                    lst["t"].fill_(i)
-                self._lane_step(sts, streams, Bl, device, fill, keep=(cur,), advance=False)
-                if self.guidance_high_priority:
-                    # the guidance on its own HIGH-priority stream: its many small kernels are dispatched ahead of the denoiser
-                    # graph's queued workgroups whenever a CU has room, instead of taking turns with whole kernels
-                    main = torch.cuda.current_stream(device)
-                    gs = self._guidance_stream(device)
-                    gs.wait_stream(main)
-                    with torch.cuda.stream(gs):
-                        shift = self.alignment_fn(cur, ts, zc=cond, y=y, **(alignment_kwargs or {})).contiguous().float()
-                    for tns in (cur, ts):
-                        tns.record_stream(gs)
-                    main.wait_stream(gs)
-                    shift.record_stream(main)
-                else:
-                    shift = self.alignment_fn(cur, ts, zc=cond, y=y, **(alignment_kwargs or {})).contiguous().float()
-                for stream in streams:
-                    torch.cuda.current_stream(device).wait_stream(stream)
-                eps = sts[0]["out"] if len(sts) == 1 else torch.cat([lst["out"] for lst in sts], dim=0)
+                eps, shift = self._aligned_eps_and_shift(eps_lanes, cur, i, ts, cond, y, alignment_kwargs, device)
                 if noise is None:
                     noise = torch.randn(shape, device=device)
                 img = self._ddpm_update(cur, eps, noise, shift, ts, 1.0, self.clip_denoised)
@@ -610,9 +625,11 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
     @torch.no_grad()
     @_on_own_device
     def ddim_sample_loop(self, cond, shape, ddim_steps=50, eta=0.0, x_T=None, noise_tape=None, return_intermediates=False,
-                         ddim_discretize="uniform"):
+                         ddim_discretize="uniform", use_alignment=False, alignment_kwargs=None, y=None):
         """DDIM over the reference's timestep subset (diffusion/utils.py:42-70).  NOT in the reference:
-        z_prev = sqrt(a_prev) z0 + sqrt(1 - a_prev - sigma^2) eps + sigma n, denoiser queried at t = steps[i]."""
+        z_prev = sqrt(a_prev) z0 + sqrt(1 - a_prev - sigma^2) eps + sigma n, denoiser queried at t = steps[i].
+        use_alignment: knowledge-aligned DDIM, z_prev -= gamma_idx * alignment_fn(z_t, steps[idx], zc=cond, y=y,
+        **alignment_kwargs) with gamma_idx from make_ddim_guidance_coefficients."""
         device = self.betas.device
         B = shape[self.batch_axis]
         if self.shorten_cond_schedule:
@@ -632,6 +649,9 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         else:
             img = torch.randn(shape, device=device)
         intermediates = [img]
+        if use_alignment:
+            return self._aligned_ddim_loop(cond, shape, steps, sig, a, a_prev, eta, img, noise_tape, intermediates, return_intermediates,
+                                           y, alignment_kwargs)
         lanes = self._lanes("ddim", B, cond, device, self.use_hip_graph and img.is_cuda and not return_intermediates)
         if lanes is not None:
             sts, streams, Bl = lanes
@@ -678,6 +698,40 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             intermediates.append(img)
         return (img, intermediates) if return_intermediates else img
 
+    def _aligned_ddim_loop(self, cond, shape, steps, sig, a, a_prev, eta, img, noise_tape, intermediates, return_intermediates, y,
+                           alignment_kwargs):
+        """Knowledge-aligned DDIM: the aligned ancestral loop's structure (denoiser-only graphs on the lane streams next to the
+        guidance on the whole batch, or eager) with pd_ddim_step_guided as the step epilogue.  Noise tape / RNG as the un-guided
+        DDIM loop: x_T, then tape[1 + k] (or a device draw when eta > 0) for step k."""
+        assert self.alignment_fn is not None, "Alignment function not set."
+        device = self.betas.device
+        B = shape[self.batch_axis]
+        gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), steps)
+        eps_lanes = None
+        if self.use_hip_graph and self.parameterization == "eps" and img.is_cuda and isinstance(cond, torch.Tensor):
+            eps_lanes = self._aligned_eps_lanes(B, cond, device)
+        coefs = torch.tensor(np.stack([a, a_prev, sig, gamma.astype(np.float64)], axis=1), dtype=torch.float32, device=device)
+        for k, idx in enumerate(reversed(range(len(steps)))):
+            coef = coefs[idx:idx + 1].expand(B, 4).contiguous()       # per-sample rows (a_t, a_prev, sigma, gamma)
+            noise = None
+            if noise_tape is not None:
+                noise = noise_tape[1 + k].to(device).contiguous()
+            elif eta > 0:
+                noise = torch.randn(shape, device=device)
+            t = int(steps[idx])
+            ts = torch.full((B,), t, device=device, dtype=torch.long)
+            cur = img.contiguous()
+            if eps_lanes is not None:
+                eps, shift = self._aligned_eps_and_shift(eps_lanes, cur, t, ts, cond, y, alignment_kwargs, device)
+            else:
+                eps = self.apply_model(cur, ts, cond).contiguous()
+                shift = self.alignment_fn(cur, ts, zc=cond, y=y, **(alignment_kwargs or {})).contiguous().float()
+            img = torch.empty_like(cur)
+            with L.on_device(cur):
+                L.ddim_step_guided(cur, eps, noise, shift, coef, img, B, cur[0].numel())
+            intermediates.append(img)
+        return (img, intermediates) if return_intermediates else img
+
     @torch.no_grad()
     @_on_own_device
     def sample(self, cond, batch_size=16, use_alignment=False, alignment_kwargs=None, return_intermediates=False, x_T=None,
@@ -702,10 +756,11 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             zc = cond if isinstance(cond, torch.Tensor) else cond.get("y", None)
         y = cond if isinstance(cond, torch.Tensor) else cond.get("y", None)
         if sampler == "ddim":
-            if use_alignment or mask is not None:
-                raise NotImplementedError("alignment / inpainting are defined for the ancestral sampler only")
+            if mask is not None:
+                raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
             output = self.ddim_sample_loop(zc, shape, ddim_steps=ddim_steps, eta=eta, x_T=x_T, noise_tape=noise_tape,
-                                           return_intermediates=return_intermediates)
+                                           return_intermediates=return_intermediates, use_alignment=use_alignment,
+                                           alignment_kwargs=alignment_kwargs, y=y)
         else:
             output = self.p_sample_loop(cond=zc, shape=shape, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
                                         return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,

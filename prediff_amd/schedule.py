@@ -70,3 +70,19 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=False)
     a_before = np.concatenate([ac[:1], ac[steps[:-1]]])
     sigma = eta * np.sqrt((1 - a_before) / (1 - a_t) * (1 - a_t / a_before))
     return sigma, a_t, a_before
+
+
+def make_ddim_guidance_coefficients(posterior_log_variance_clipped, ddim_timesteps) -> np.ndarray:
+    """gamma per DDIM step of the knowledge-aligned DDIM sampler: step idx moves from t = steps[idx] to the alpha of
+    steps[idx-1] and skips the DDPM timesteps J_idx = {steps[idx-1] + 1, ..., steps[idx]} ({0, ..., steps[0]} for idx = 0); it
+    subtracts gamma_idx * g with gamma_idx = sum over J_idx of exp(0.5 * logvar_clipped[j]), the mean shifts the reference's aligned
+    ancestral chain applies over those timesteps.  A repeated grid point (quad's integer rounding, the T-1 clamp) has an empty J and
+    gamma 0.  fp64 from the fp32 buffer, one rounding to fp32 at the end."""
+    sd = np.exp(0.5 * np.asarray(posterior_log_variance_clipped, dtype=np.float32).astype(np.float64))
+    steps = np.asarray(ddim_timesteps, dtype=np.int64)
+    gamma = np.zeros(len(steps), dtype=np.float64)
+    lo = 0
+    for idx, t in enumerate(steps):
+        gamma[idx] = sd[lo:t + 1].sum()          # empty when t < lo
+        lo = max(lo, int(t) + 1)
+    return gamma.astype(np.float32)
