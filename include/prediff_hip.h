@@ -348,6 +348,27 @@ int pd_ffn_rows(const float* x, float* out, const void* wffn, const float* vecs,
 int pd_sevir_skill_counts(const float* pred, const float* target, const float* thresholds, int nthr, float divisor,
                           long long* counts, int64_t outer, int T, int64_t inner, int keep_seq, pd_stream_t stream);
 
+/* SEVIRSkillScore.update with preprocess_type "sevir_pool{s}" (datasets/sevir/evaluation.py:220-231): pred and target are max-pooled over
+ * (H, W) with kernel = stride = pool for each (N, T, C) (floor mode; a NaN in a window makes the cell NaN), divided by divisor, then counted
+ * as pd_sevir_skill_counts does into the same counts[thr][t][3] (keep_seq) or counts[thr][3].  sizes: host int64[5] = N, T, H, W, C;
+ * pred_strides / target_strides: host int64[5], the element strides of those axes (any layout is read in place; a missing axis has
+ * size 1).  nthr <= 8. */
+int pd_sevir_skill_counts_pooled(const float* pred, const float* target, const float* thresholds, int nthr, float divisor,
+                                 long long* counts, const int64_t* sizes, const int64_t* pred_strides, const int64_t* target_strides,
+                                 int pool, int keep_seq, pd_stream_t stream);
+
+/* Ensemble verification (not in the reference): ens holds M members of target's shape (1 <= M <= 512), both preprocessed like
+ * pd_sevir_skill_counts_pooled (pool = 1: no pooling).  A pooled pixel is valid when the target and all members are non-NaN there; per
+ * valid pixel of step t (t = 0 unless keep_seq) it adds 1 to n_valid[t] (int64), (c - M o)^2 to brier[thr][t] (int64, exact; c = #{x_i >=
+ * thr}, o = [y >= thr]) and, in fp64, sum_i |x_i - y| to sums[0][t], sum_ij |x_i - x_j| to sums[1][t], (mean - y)^2 to sums[2][t] and
+ * sum_i (x_i - mean)^2 / (M - 1) (0 for M = 1) to sums[3][t].  The fp64 sums are reduced in a fixed order (bit-reproducible).
+ * sizes: host int64[5] = N, T, H, W, C; ens_strides: host int64[6] = member, N, T, H, W, C strides; target_strides: host int64[5].
+ * ws: device workspace of pd_ensemble_score_ws_doubles(M, sizes, pool) doubles (-1: unsupported M / sizes). */
+int64_t pd_ensemble_score_ws_doubles(int M, const int64_t* sizes, int pool);
+int pd_ensemble_score_update(const float* ens, const float* target, const float* thresholds, int nthr, float divisor, int M,
+                             const int64_t* sizes, const int64_t* ens_strides, const int64_t* target_strides, int pool, int keep_seq,
+                             long long* n_valid, long long* brier, double* sums, double* ws, int64_t ws_doubles, pd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,10 @@ _PROTOS = {
     "pd_ffn_rows_supported": (C.c_int, [C.c_int] * 3),
     "pd_ffn_rows": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_float, C.POINTER(CallOpts), C.c_void_p]),
     "pd_sevir_skill_counts": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    "pd_sevir_skill_counts_pooled": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_float] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
+    "pd_ensemble_score_ws_doubles": (C.c_int64, [C.c_int, C.c_void_p, C.c_int]),
+    "pd_ensemble_score_update": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int]
+                                 + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -429,6 +433,29 @@ def nhwc_to_nchw(x, out, N, Cn, HW, ld_in):
 def sevir_skill_counts(pred, target, thresholds, divisor, counts, outer, T, inner, keep_seq):
     _check(lib().pd_sevir_skill_counts(ptr(pred), ptr(target), ptr(thresholds), thresholds.numel(), divisor, ptr(counts), outer, T,
                                        inner, 1 if keep_seq else 0, stream_ptr()), "pd_sevir_skill_counts")
+
+
+def _i64(vals):
+    vals = [int(v) for v in vals]
+    return (C.c_int64 * len(vals))(*vals)
+
+
+def sevir_skill_counts_pooled(pred, target, thresholds, divisor, counts, sizes, pred_strides, target_strides, pool, keep_seq):
+    """sizes / strides: the (N, T, H, W, C) sizes and element strides of pred and target (a missing axis: size 1, stride 0)."""
+    _check(lib().pd_sevir_skill_counts_pooled(ptr(pred), ptr(target), ptr(thresholds), thresholds.numel(), divisor, ptr(counts),
+                                              _i64(sizes), _i64(pred_strides), _i64(target_strides), int(pool), 1 if keep_seq else 0,
+                                              stream_ptr()), "pd_sevir_skill_counts_pooled")
+
+
+def ensemble_score_ws_doubles(M, sizes, pool):
+    return int(lib().pd_ensemble_score_ws_doubles(int(M), _i64(sizes), int(pool)))
+
+
+def ensemble_score_update(ens, target, thresholds, divisor, M, sizes, ens_strides, target_strides, pool, keep_seq, n_valid, brier, sums, ws):
+    """ens_strides: member stride followed by the (N, T, H, W, C) strides; n_valid int64 [T'], brier int64 [thr, T'], sums fp64 [4, T']."""
+    _check(lib().pd_ensemble_score_update(ptr(ens), ptr(target), ptr(thresholds), thresholds.numel(), divisor, int(M), _i64(sizes),
+                                          _i64(ens_strides), _i64(target_strides), int(pool), 1 if keep_seq else 0, ptr(n_valid), ptr(brier),
+                                          ptr(sums), ptr(ws), ws.numel(), stream_ptr()), "pd_ensemble_score_update")
 
 
 def attn_block_fused_supported(Cn, heads, vol):

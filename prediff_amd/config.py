@@ -123,8 +123,11 @@ def split_sequence(seq: torch.Tensor, in_len: int, out_len: int):
 
 @torch.no_grad()
 def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int = 0, rank: int = 0, npy_dir: Optional[str] = None,
-                     score=None, aligned_score=None, **sample_kwargs):
-    """The sampling part of test_step (train_sevirlr_prediff.py:905-979) for one batch of sequences (B, in_len+out_len, H, W, C)."""
+                     score=None, aligned_score=None, ensemble_score=None, aligned_ensemble_score=None, **sample_kwargs):
+    """The sampling part of test_step (train_sevirlr_prediff.py:905-979) for one batch of sequences (B, in_len+out_len, H, W, C).
+
+    ensemble_score / aligned_ensemble_score (ensemble_score.SEVIREnsembleScore, layout of the sequences; not in the reference): after the
+    loop, updated once with the stacked samples, M = num_samples_per_context members of each of the B contexts."""
     import numpy as np
     from .alignment import get_alignment_kwargs_avg_x
     lay, ev = cfg["layout"], cfg["eval"]
@@ -148,4 +151,8 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
             if score is not None:
                 score.update(pred.float(), tgt)
             out["pred"].append(pred)
+    if ensemble_score is not None and out["pred"]:
+        ensemble_score.update(torch.stack(out["pred"]).float(), tgt)
+    if aligned_ensemble_score is not None and out["aligned_pred"]:
+        aligned_ensemble_score.update(torch.stack(out["aligned_pred"]).float(), tgt)
     return out

@@ -2,11 +2,14 @@
 (datasets/sevir/evaluation.py:88-285) without the torchmetrics dependency.
 
 Same constructor keywords, ``update(pred, target)`` / ``compute()`` / ``reset()`` and result dictionary; the counting
-(the only per-pixel work) is ONE launch of pd_sevir_skill_counts instead of the reference's per-threshold loop.  Counts
+(the only per-pixel work) is ONE launch of pd_sevir_skill_counts instead of the reference's per-threshold loop.
+``preprocess_type="sevir_pool{s}"`` (evaluation.py:220-231: max-pool over (H, W) with kernel = stride = s, the CSI-pool4 /
+CSI-pool16 scores) is one launch of pd_sevir_skill_counts_pooled, which reads the frames in place through their strides in any
+5-letter layout (the reference's rearrange needs all of N, T, H, W, C, so a 4-letter layout is refused at construction).  Counts
 are exact int64, so scores match the reference bit for bit given the same frames.  `sync()` sums the counters over the
 ranks of a process group (what torchmetrics' dist_reduce_fx="sum" does at compute time).
 """
-import math
+import re
 from typing import Optional, Sequence
 
 import numpy as np
@@ -14,13 +17,42 @@ import torch
 
 from . import _lib as L
 
+AXES = "NTHWC"
+
+
+def parse_preprocess(preprocess_type: str, layout: str) -> int:
+    """Pool scale of a preprocess_type ("sevir": 1, "sevir_pool{s}": s, the first integer in the string as in the reference);
+    a pooled preprocess needs a layout that names N, T, H, W and C."""
+    if preprocess_type == "sevir":
+        return 1
+    if not preprocess_type.startswith("sevir_pool"):
+        raise NotImplementedError(f"preprocess_type {preprocess_type!r}: only 'sevir' and 'sevir_pool{{s}}' are implemented")
+    m = re.search(r"\d+", preprocess_type)
+    if m is None or int(m.group()) < 1:
+        raise ValueError(f"preprocess_type {preprocess_type!r}: no positive pool scale")
+    if sorted(layout) != sorted(AXES):
+        raise ValueError(f"preprocess_type {preprocess_type!r} pools over H and W and needs a layout of the letters N, T, H, W, C; "
+                         f"got {layout!r}")
+    return int(m.group())
+
+
+def axes_of(layout: str, x: torch.Tensor, lead: int = 0):
+    """(sizes, strides) of x's N, T, H, W, C axes (after `lead` leading axes); an axis the layout does not name has size 1, stride 0."""
+    sizes, strides = [], []
+    for a in AXES:
+        i = layout.find(a)
+        sizes.append(x.shape[lead + i] if i >= 0 else 1)
+        strides.append(x.stride(lead + i) if i >= 0 else 0)
+    return sizes, strides
+
 
 class SEVIRSkillScore:
     def __init__(self, layout: str = "NHWT", mode: str = "0", seq_len: Optional[int] = None, preprocess_type: str = "sevir",
                  threshold_list: Sequence[int] = (16, 74, 133, 160, 181, 219),
                  metrics_list: Sequence[str] = ("csi", "bias", "sucr", "pod"), eps: float = 1e-4):
-        if preprocess_type != "sevir":
-            raise NotImplementedError("only preprocess_type='sevir' (no pooling) is implemented")
+        self.preprocess_type = preprocess_type
+        self.pool_scale = parse_preprocess(preprocess_type, layout)
+        self.pooled = preprocess_type != "sevir"
         if mode not in ("0", "1", "2"):
             raise NotImplementedError(f"mode {mode} not supported!")
         self.layout, self.mode, self.seq_len = layout, mode, seq_len
@@ -69,6 +101,13 @@ class SEVIRSkillScore:
             self._counts = torch.zeros((len(self.threshold_list), T if self.keep_seq_len_dim else 1, 3), dtype=torch.int64, device=dev)
             self._thr = torch.tensor(self.threshold_list, dtype=torch.float32, device=dev)
         divisor = float(np.float32(1.0 / 255.0))       # data.float() / PREPROCESS_SCALE_01['vil'] (sevir_dataloader.py:679)
+        if self.pooled:
+            p, q = pred.detach().float(), target.detach().float()       # read in place through their strides
+            sizes, ps = axes_of(self.layout, p)
+            _, qs = axes_of(self.layout, q)
+            with L.on_device(pred):
+                L.sevir_skill_counts_pooled(p, q, self._thr, divisor, self._counts, sizes, ps, qs, self.pool_scale, self.keep_seq_len_dim)
+            return
         with L.on_device(pred):
             L.sevir_skill_counts(pred.detach().float().contiguous(), target.detach().float().contiguous(), self._thr, divisor,
                                  self._counts, outer, T, inner, self.keep_seq_len_dim)
