@@ -155,7 +155,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         # Default: two lanes from 8 trajectories per lane on, ONE below that (MI355X, round 5: 16 trajectories 1345-1358 steps/s in two lanes vs
         # 1293-1325 in one, but 12: 1020 vs 1089 and 8: 918 vs 951 -- profiles/r05_r_small_batch_lanes.txt).  Assigning `num_streams` pins it.
         self._num_streams, self._lanes_pinned = 2, False
-        self.aligned_lanes = 1        # knowledge-aligned loop: denoiser lanes next to the guidance stream (see p_sample_loop)
+        self.aligned_lanes = 1        # knowledge-aligned loops: denoiser lanes next to the guidance stream (see _aligned_eps_lanes)
         self.guidance_high_priority = False   # knowledge-aligned loop: run the guidance on a high-priority side stream (A/B switch;
                                               # measured neutral: 32.9 vs 32.8-33.1 ms at 32 trajectories, 11.5 vs 11.6 ms at 8)
         self._guidance_streams: Dict = {}
@@ -362,12 +362,14 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             return self._p_sample_torch(zt, zc, t, y, use_alignment, alignment_kwargs, clip_denoised, return_x0, temperature,
                                         noise_dropout, score_corrector, corrector_kwargs, noise)
         eps = self.apply_model(zt, t, zc)
-        shift = None
-        if use_alignment:
-            shift = self.alignment_fn(zt, t, zc=zc, y=y, **(alignment_kwargs or {})).contiguous().float()
+        shift = self._guidance(zt, t, zc, y, alignment_kwargs) if use_alignment else None
         if noise is None:
             noise = torch.randn(zt.shape, device=zt.device)
         return self._ddpm_update(zt, eps, noise, shift, t, temperature, clip_denoised)
+
+    def _guidance(self, zt, t, zc, y, alignment_kwargs):
+        """The alignment shift alignment_fn(z_t, t, zc, y, **alignment_kwargs) as a contiguous fp32 tensor."""
+        return self.alignment_fn(zt, t, zc=zc, y=y, **(alignment_kwargs or {})).contiguous().float()
 
     def _ddpm_update(self, zt, eps, noise, shift, t, temperature=1.0, clip_denoised=False, out=None):
         B = zt.shape[0]
@@ -470,17 +472,20 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
     @staticmethod
     def _lane_step(sts, streams, Bl, device, fill, keep=(), advance=True):
         """One step of every lane: `fill(st, sl)` writes the lane's inputs (slice sl of the batch) on the lane's stream, then the
-        lane's graph is replayed and its latent advanced in place.  `keep`: tensors made on the caller's stream that `fill` reads."""
+        lane's graph is replayed and its latent advanced in place.  `keep`: tensors made on the caller's stream that `fill` reads.
+        A lane on the caller's own stream (the single graph) needs neither the wait nor `keep`."""
         main = torch.cuda.current_stream(device)
         for l, (st, stream) in enumerate(zip(sts, streams)):
-            stream.wait_stream(main)                  # inputs produced on the caller's stream (noise draws, schedules)
+            side = stream != main
+            if side:
+                stream.wait_stream(main)              # inputs produced on the caller's stream (noise draws, schedules)
             with torch.cuda.stream(stream):
                 fill(st, slice(l * Bl, (l + 1) * Bl))
                 st["graph"].replay()
                 if advance:
                     st["z"].copy_(st["out"])
             for t in keep:
-                if t is not None:
+                if t is not None and side:
                     t.record_stream(stream)           # the caching allocator must not recycle it before the lane has read it
 
     def _aligned_eps_lanes(self, B, cond, device):
@@ -522,19 +527,122 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             gs = self._guidance_stream(device)
             gs.wait_stream(main)
             with torch.cuda.stream(gs):
-                shift = self.alignment_fn(cur, ts, zc=cond, y=y, **(alignment_kwargs or {})).contiguous().float()
+                shift = self._guidance(cur, ts, cond, y, alignment_kwargs)
             for tns in (cur, ts):
                 tns.record_stream(gs)
             main.wait_stream(gs)
             shift.record_stream(main)
         else:
-            shift = self.alignment_fn(cur, ts, zc=cond, y=y, **(alignment_kwargs or {})).contiguous().float()
+            shift = self._guidance(cur, ts, cond, y, alignment_kwargs)
         for stream in streams:
             torch.cuda.current_stream(device).wait_stream(stream)
         eps = sts[0]["out"] if len(sts) == 1 else torch.cat([lst["out"] for lst in sts], dim=0)
         return eps, shift
 
     # ------------------------------------------------------------------------------------------------ loops
+    @staticmethod
+    def _start_latent(x_T, noise_tape, shape, device):
+        """The starting latent: x_T, else noise_tape[0], else a device draw.  A step-ordered (lazy) tape still owes draw 0 when the
+        caller gives x_T: it is consumed and the caller's x_T kept."""
+        if noise_tape is not None:
+            first = noise_tape[0]
+            return x_T if x_T is not None else first.to(device)
+        return x_T if x_T is not None else torch.randn(shape, device=device)
+
+    @staticmethod
+    def _step_noise(noise_tape, k, device, draw=None, per_step=1, slot=0):
+        """Draw `slot` of step k: noise_tape[1 + per_step * k + slot] (per_step = 2 with shorten_cond_schedule, whose steps draw
+        [c_k, n_k]).  Tapes are read strictly in order: ensemble._LazyTape keeps only its last entry.  Without a tape, `draw()`, or
+        None when `draw` is None."""
+        if noise_tape is not None:
+            return noise_tape[1 + per_step * k + slot].to(device).contiguous()
+        return draw() if draw is not None else None
+
+    def _run_sampler(self, kind, cond, shape, x_T, noise_tape, visits, epilogue, coefs=None, draw=None, eager=None,
+                     use_alignment=False, y=None, alignment_kwargs=None, return_intermediates=False, log_every_t=1, mask=None,
+                     x0=None, callback=None, img_callback=None):
+        """The step loop of every sampler.  One of four modes is chosen once per call:
+          lanes   -- one `kind` graph per equal sub-batch, each replayed on its own stream (no per-step hooks; see _lanes);
+          graph   -- one `kind` graph replayed on the caller's stream;
+          aligned -- use_alignment: denoiser-only ("eps") graphs next to the guidance on the whole batch, then `epilogue`;
+          eager   -- no graphs: `eager(img, ts, noise, cond)` (the ancestral loop's p_sample), else denoiser, guidance, `epilogue`.
+        Graphs need use_hip_graph, a CUDA latent, a tensor condition (a dict / None cannot be a static graph input), eps
+        parameterisation and no shorten_cond_schedule (the condition changes every step).
+        visits: (t, row) per step in visiting order; `row` picks the step's coefficients from the device table `coefs`.
+        epilogue(cur, eps, shift, ts, row, noise) -> the next latent; `shift` is None without alignment.
+        Step noise: _step_noise, drawn from the device generator at the start of the step with draw="early", where the step
+        needs it with draw="late" (the reference's ancestral order: after the denoiser and the guidance), zero with None."""
+        device = self.betas.device
+        B = shape[self.batch_axis]
+        img = self._start_latent(x_T, noise_tape, shape, device)
+
+        def randn():
+            return torch.randn(shape, device=device)
+        shorten = self.shorten_cond_schedule
+        graphs = (self.use_hip_graph and img.is_cuda and isinstance(cond, torch.Tensor) and self.parameterization == "eps"
+                  and not shorten)
+        hooks = return_intermediates or mask is not None or callback is not None or img_callback is not None
+        lanes = graph = eps_lanes = None
+        if use_alignment:
+            eps_lanes = self._aligned_eps_lanes(B, cond, device) if graphs else None
+        elif graphs:
+            lanes = self._lanes(kind, B, cond, device, not hooks)
+            graph = lanes if lanes is not None else ([self._graph_step(kind, B, cond, device)], [torch.cuda.current_stream(device)], B)
+        if lanes is not None:
+            sts, _, Bl = lanes
+            for l, st in enumerate(sts):
+                st["z"].copy_(img[l * Bl:(l + 1) * Bl])
+        intermediates = [img]
+        for k, (t, row) in enumerate(visits):
+            if shorten:      # the conditioning latents re-noised in front of the step (cumulative, as in the reference)
+                cn = self._step_noise(noise_tape, k, device, lambda: torch.randn_like(cond), per_step=2)
+                cond = self.q_sample(cond, self.cond_ids[torch.full((B,), t, device=device, dtype=torch.long)], noise=cn)
+            noise = self._step_noise(noise_tape, k, device, randn if draw == "early" else None, 1 + shorten, int(shorten))
+            if graph is not None:
+                if noise is None and draw == "late" and lanes is not None:
+                    noise = randn()               # one whole-batch draw (the reference's RNG order), sliced per lane
+
+                def fill(st, sl):
+                    if lanes is None:
+                        st["z"].copy_(img)
+                    st["t"].fill_(t)
+                    if row is not None:
+                        st["coef"].copy_(coefs[row])
+                    if noise is not None:
+                        st["noise"].copy_(noise[sl])
+                    else:
+                        st["noise"].normal_() if draw == "late" else st["noise"].zero_()
+                self._lane_step(*graph, device, fill, keep=(noise,), advance=lanes is not None)
+                if lanes is None:
+                    img = graph[0][0]["out"].clone()
+            else:
+                ts = torch.full((B,), t, device=device, dtype=torch.long)
+                if eps_lanes is None and eager is not None:
+                    img = eager(img, ts, noise, cond)
+                else:
+                    cur = img.contiguous()
+                    if eps_lanes is not None:
+                        eps, shift = self._aligned_eps_and_shift(eps_lanes, cur, t, ts, cond, y, alignment_kwargs, device)
+                    else:
+                        eps = self.apply_model(cur, ts, cond).contiguous()
+                        shift = self._guidance(cur, ts, cond, y, alignment_kwargs) if use_alignment else None
+                    if noise is None and draw == "late":
+                        noise = randn()
+                    img = epilogue(cur, eps, shift, ts, row, noise)
+            if mask is not None:
+                img = self.q_sample(x0, torch.full((B,), t, device=device, dtype=torch.long)) * mask + (1.0 - mask) * img
+            if return_intermediates and (t % log_every_t == 0 or k == 0):
+                intermediates.append(img)
+            if callback:
+                callback(t)
+            if img_callback:
+                img_callback(img, t)
+        if lanes is not None:
+            for stream in lanes[1]:
+                torch.cuda.current_stream(device).wait_stream(stream)
+            img = torch.cat([st["z"] for st in lanes[0]], dim=0)
+        return (img, intermediates) if return_intermediates else img
+
     @torch.no_grad()
     @_on_own_device
     def p_sample_loop(self, cond, shape, y=None, use_alignment=False, alignment_kwargs=None, return_intermediates=False,
@@ -543,84 +651,22 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         """Ancestral loop t = timesteps-1 .. 0 (latent_diffusion.py:633-684).  RNG draw order as the reference:
         [x_T, noise_{T-1}, ..., noise_0] from the device's default generator, unless `noise_tape` supplies them.  With
         shorten_cond_schedule every step draws the conditioning noise first: [x_T, c_{T-1}, noise_{T-1}, ..., c_0, noise_0]."""
-        log_every_t = log_every_t or self.log_every_t
-        device = self.betas.device
-        B = shape[self.batch_axis]
-        if x_T is not None:
-            img = x_T
-            if noise_tape is not None:
-                noise_tape[0]             # a step-ordered (lazy) tape still owes draw 0 = x_T: consume it, keep the caller's x_T
-        elif noise_tape is not None:
-            img = noise_tape[0].to(device)
-        else:
-            img = torch.randn(shape, device=device)
-        intermediates = [img]
         timesteps = self.num_timesteps if timesteps is None else timesteps
         if start_T is not None:
             timesteps = min(timesteps, start_T)
         if mask is not None:
             assert x0 is not None
-        shorten = self.shorten_cond_schedule          # the condition changes every step: eager path
-        use_graph = (self.use_hip_graph and not use_alignment and self.parameterization == "eps" and img.is_cuda
-                     and isinstance(cond, torch.Tensor) and not shorten)   # a dict / None condition cannot be a static graph input: eager path
-        lanes = self._lanes("ddpm", B, cond, device, use_graph and mask is None and callback is None and img_callback is None
-                            and not return_intermediates)
-        if lanes is not None:
-            # independent sub-batches, one HIP stream each; noise is drawn for the whole batch (reference RNG order) and sliced
-            sts, streams, Bl = lanes
-            for l, st in enumerate(sts):
-                st["z"].copy_(img[l * Bl:(l + 1) * Bl])
-            for k, i in enumerate(reversed(range(0, timesteps))):
-                noise = noise_tape[1 + k].to(device) if noise_tape is not None else torch.randn(shape, device=device)
 
-                def fill(st, sl, i=i, noise=noise):
-                    st["t"].fill_(i)
-                    st["noise"].copy_(noise[sl])
-                self._lane_step(sts, streams, Bl, device, fill, keep=(noise,))
-            for stream in streams:
-                torch.cuda.current_stream(device).wait_stream(stream)
-            return torch.cat([st["z"] for st in sts], dim=0)
-        # knowledge alignment: the guidance gradient depends on z_t only, not on eps, so it runs (PyTorch autograd, caller's stream)
-        # concurrently with the denoiser graphs of the lanes; the step epilogue joins them.  Same arithmetic as the eager path.
-        eps_lanes = None
-        if use_alignment and self.use_hip_graph and self.parameterization == "eps" and img.is_cuda and isinstance(cond, torch.Tensor) and not shorten:
-            eps_lanes = self._aligned_eps_lanes(B, cond, device)
-        st = self._graph_step("ddpm", B, cond, device) if use_graph else None
-        for k, i in enumerate(reversed(range(0, timesteps))):
-            if shorten:
-                ts = torch.full((B,), i, device=device, dtype=torch.long)
-                cn = noise_tape[1 + 2 * k].to(device) if noise_tape is not None else torch.randn_like(cond)
-                cond = self.q_sample(cond, self.cond_ids[ts], noise=cn)       # (cumulative, as in the reference: `cond` is overwritten)
-                noise = noise_tape[2 + 2 * k].to(device) if noise_tape is not None else None
-            else:
-                noise = noise_tape[1 + k].to(device) if noise_tape is not None else None
-            if eps_lanes is not None:
-                ts = torch.full((B,), i, device=device, dtype=torch.long)
-                cur = img
-                eps, shift = self._aligned_eps_and_shift(eps_lanes, cur, i, ts, cond, y, alignment_kwargs, device)
-                if noise is None:
-                    noise = torch.randn(shape, device=device)
-                img = self._ddpm_update(cur, eps, noise, shift, ts, 1.0, self.clip_denoised)
-            elif st is not None:
-                st["z"].copy_(img)
-                st["t"].fill_(i)
-                st["noise"].copy_(noise) if noise is not None else st["noise"].normal_()
-                st["graph"].replay()
-                img = st["out"].clone()
-            else:
-                ts = torch.full((B,), i, device=device, dtype=torch.long)
-                img = self.p_sample(zt=img, zc=cond, t=ts, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
-                                    clip_denoised=self.clip_denoised, noise=noise)
-            if mask is not None:
-                ts = torch.full((B,), i, device=device, dtype=torch.long)
-                img = self.q_sample(x0, ts) * mask + (1.0 - mask) * img
-            if i % log_every_t == 0 or i == timesteps - 1:
-                intermediates.append(img)
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(img, i)
-        return (img, intermediates) if return_intermediates else img
+        def eager(img, ts, noise, cond):
+            return self.p_sample(zt=img, zc=cond, t=ts, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
+                                 clip_denoised=self.clip_denoised, noise=noise)
+
+        def epilogue(cur, eps, shift, ts, row, noise):
+            return self._ddpm_update(cur, eps, noise, shift, ts, 1.0, self.clip_denoised)
+        return self._run_sampler("ddpm", cond, shape, x_T, noise_tape, [(i, None) for i in reversed(range(timesteps))], epilogue,
+                                 draw="late", eager=eager, use_alignment=use_alignment, y=y, alignment_kwargs=alignment_kwargs,
+                                 return_intermediates=return_intermediates, log_every_t=log_every_t or self.log_every_t, mask=mask,
+                                 x0=x0, callback=callback, img_callback=img_callback)
 
     @torch.no_grad()
     @_on_own_device
@@ -629,8 +675,8 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         """DDIM over the reference's timestep subset (diffusion/utils.py:42-70).  NOT in the reference:
         z_prev = sqrt(a_prev) z0 + sqrt(1 - a_prev - sigma^2) eps + sigma n, denoiser queried at t = steps[i].
         use_alignment: knowledge-aligned DDIM, z_prev -= gamma_idx * alignment_fn(z_t, steps[idx], zc=cond, y=y,
-        **alignment_kwargs) with gamma_idx from make_ddim_guidance_coefficients."""
-        device = self.betas.device
+        **alignment_kwargs) with gamma_idx from make_ddim_guidance_coefficients.  Noise tape / RNG: x_T, then tape[1 + k] (or a
+        device draw when eta > 0) for step k."""
         B = shape[self.batch_axis]
         if self.shorten_cond_schedule:
             raise NotImplementedError("shorten_cond_schedule (num_timesteps_cond > 1) is defined for the ancestral loop only")
@@ -638,99 +684,31 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             raise ValueError(f"ddim_steps must be in [1, {self.num_timesteps}], got {ddim_steps}")
         if self.clip_denoised:
             raise NotImplementedError("clip_denoised=True is defined for the ancestral sampler only (the DDIM step has no clamp)")
+        if self.parameterization != "eps":
+            raise NotImplementedError('parameterization="x0" is defined for the ancestral sampler only (the DDIM step reads the '
+                                      "model output as eps)")
+        if use_alignment:
+            assert self.alignment_fn is not None, "Alignment function not set."
         steps = np.minimum(make_ddim_timesteps(ddim_discretize, ddim_steps, self.num_timesteps), self.num_timesteps - 1)
         sig, a, a_prev = make_ddim_sampling_parameters(self._alphas_cumprod_f64.astype(np.float32).astype(np.float64), steps, eta)
-        if x_T is not None:
-            img = x_T
-            if noise_tape is not None:
-                noise_tape[0]             # see p_sample_loop
-        elif noise_tape is not None:
-            img = noise_tape[0].to(device)
-        else:
-            img = torch.randn(shape, device=device)
-        intermediates = [img]
+        cols = [a, a_prev, sig]
         if use_alignment:
-            return self._aligned_ddim_loop(cond, shape, steps, sig, a, a_prev, eta, img, noise_tape, intermediates, return_intermediates,
-                                           y, alignment_kwargs)
-        lanes = self._lanes("ddim", B, cond, device, self.use_hip_graph and img.is_cuda and not return_intermediates)
-        if lanes is not None:
-            sts, streams, Bl = lanes
-            for l, st in enumerate(sts):
-                st["z"].copy_(img[l * Bl:(l + 1) * Bl])
-            for k, idx in enumerate(reversed(range(len(steps)))):
-                coef = torch.tensor([[a[idx], a_prev[idx], sig[idx]]], dtype=torch.float32).repeat(Bl, 1).to(device)
-                noise = None
-                if noise_tape is not None:
-                    noise = noise_tape[1 + k].to(device)
-                elif eta > 0:
-                    noise = torch.randn(shape, device=device)
+            cols.append(make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), steps))
+        # one row (a_t, a_prev, sigma[, gamma]) per step, rounded from fp64 to fp32 once
+        coefs = torch.tensor(np.stack(cols, axis=1), dtype=torch.float32, device=self.betas.device)
 
-                def fill(st, sl, t=int(steps[idx]), coef=coef, noise=noise):
-                    st["t"].fill_(t)
-                    st["coef"].copy_(coef)
-                    st["noise"].copy_(noise[sl]) if noise is not None else st["noise"].zero_()
-                self._lane_step(sts, streams, Bl, device, fill, keep=(coef, noise))
-            for stream in streams:
-                torch.cuda.current_stream(device).wait_stream(stream)
-            return torch.cat([st["z"] for st in sts], dim=0)
-        # a dict / None condition cannot be a static graph input: eager path
-        st = self._graph_step("ddim", B, cond, device) if (self.use_hip_graph and img.is_cuda and isinstance(cond, torch.Tensor)) else None
-        for k, idx in enumerate(reversed(range(len(steps)))):
-            coef = torch.tensor([[a[idx], a_prev[idx], sig[idx]]], dtype=torch.float32).repeat(B, 1)
-            noise = None
-            if noise_tape is not None:
-                noise = noise_tape[1 + k].to(device)
-            elif eta > 0:
-                noise = torch.randn(shape, device=device)
-            if st is not None:
-                st["z"].copy_(img)
-                st["t"].fill_(int(steps[idx]))
-                st["coef"].copy_(coef)
-                st["noise"].copy_(noise) if noise is not None else st["noise"].zero_()
-                st["graph"].replay()
-                img = st["out"].clone()
-            else:
-                ts = torch.full((B,), int(steps[idx]), device=device, dtype=torch.long)
-                eps = self.apply_model(img, ts, cond)
-                out = torch.empty_like(img)
-                L.ddim_step(img.contiguous(), eps, noise if noise is not None else torch.zeros_like(img), coef.to(device), out, B, img[0].numel())
-                img = out
-            intermediates.append(img)
-        return (img, intermediates) if return_intermediates else img
-
-    def _aligned_ddim_loop(self, cond, shape, steps, sig, a, a_prev, eta, img, noise_tape, intermediates, return_intermediates, y,
-                           alignment_kwargs):
-        """Knowledge-aligned DDIM: the aligned ancestral loop's structure (denoiser-only graphs on the lane streams next to the
-        guidance on the whole batch, or eager) with pd_ddim_step_guided as the step epilogue.  Noise tape / RNG as the un-guided
-        DDIM loop: x_T, then tape[1 + k] (or a device draw when eta > 0) for step k."""
-        assert self.alignment_fn is not None, "Alignment function not set."
-        device = self.betas.device
-        B = shape[self.batch_axis]
-        gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), steps)
-        eps_lanes = None
-        if self.use_hip_graph and self.parameterization == "eps" and img.is_cuda and isinstance(cond, torch.Tensor):
-            eps_lanes = self._aligned_eps_lanes(B, cond, device)
-        coefs = torch.tensor(np.stack([a, a_prev, sig, gamma.astype(np.float64)], axis=1), dtype=torch.float32, device=device)
-        for k, idx in enumerate(reversed(range(len(steps)))):
-            coef = coefs[idx:idx + 1].expand(B, 4).contiguous()       # per-sample rows (a_t, a_prev, sigma, gamma)
-            noise = None
-            if noise_tape is not None:
-                noise = noise_tape[1 + k].to(device).contiguous()
-            elif eta > 0:
-                noise = torch.randn(shape, device=device)
-            t = int(steps[idx])
-            ts = torch.full((B,), t, device=device, dtype=torch.long)
-            cur = img.contiguous()
-            if eps_lanes is not None:
-                eps, shift = self._aligned_eps_and_shift(eps_lanes, cur, t, ts, cond, y, alignment_kwargs, device)
-            else:
-                eps = self.apply_model(cur, ts, cond).contiguous()
-                shift = self.alignment_fn(cur, ts, zc=cond, y=y, **(alignment_kwargs or {})).contiguous().float()
-            img = torch.empty_like(cur)
+        def epilogue(cur, eps, shift, ts, row, noise):
+            out = torch.empty_like(cur)
+            coef = coefs[row].expand(B, coefs.shape[1]).contiguous()
             with L.on_device(cur):
-                L.ddim_step_guided(cur, eps, noise, shift, coef, img, B, cur[0].numel())
-            intermediates.append(img)
-        return (img, intermediates) if return_intermediates else img
+                if shift is None:
+                    L.ddim_step(cur, eps, noise if noise is not None else torch.zeros_like(cur), coef, out, B, cur[0].numel())
+                else:
+                    L.ddim_step_guided(cur, eps, noise, shift, coef, out, B, cur[0].numel())
+            return out
+        return self._run_sampler("ddim", cond, shape, x_T, noise_tape, [(int(steps[idx]), idx) for idx in reversed(range(len(steps)))],
+                                 epilogue, coefs=coefs, draw="early" if eta > 0 else None, use_alignment=use_alignment, y=y,
+                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates)
 
     @torch.no_grad()
     @_on_own_device

@@ -230,6 +230,27 @@ def test_tiny_guided_ddim_vs_oracle_and_paths():
 
 
 @pytest.mark.gpu
+def test_aligned_generator_draws_same_in_every_mode():
+    """No tape: the aligned ancestral loop draws each step's noise after the denoiser and the guidance, guided DDIM (eta = 1) at the
+    start of the step.  One or two denoiser lanes next to the guidance and the eager loop consume the device generator alike: the
+    same latents bit for bit under one seed."""
+    ldm, cfg, _ = _tiny_ldm()
+    al = _tiny_alignment()
+    al.model.cuda()
+    ldm.set_alignment(al.get_mean_shift)
+    B = 2
+    zc = seeded_input("gdzc", (B,) + tuple(cfg["input_shape"]), 21).cuda()
+    ak = {"avg_x_gt": torch.tensor([[0.4], [0.1]]).cuda()}
+    for kw in (dict(timesteps=3), dict(sampler="ddim", ddim_steps=4, eta=1.0)):
+        outs = []
+        for lanes, graph in ((1, True), (2, True), (1, False)):
+            ldm.aligned_lanes, ldm.use_hip_graph = lanes, graph
+            torch.manual_seed(31)
+            outs.append(ldm.sample(cond=zc, batch_size=B, use_alignment=True, alignment_kwargs=ak, return_decoded=False, **kw))
+        assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), kw
+
+
+@pytest.mark.gpu
 def test_evaluate_context_ddim_aligned():
     from prediff_amd import config as CFG
     from prediff_amd.alignment import get_alignment_kwargs_avg_x

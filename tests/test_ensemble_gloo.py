@@ -32,13 +32,14 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, M, q):
+def _worker(rank, world, port, M, q, done):
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         y = torch.full((1, 3, 8, 8, 1), 0.25)
         out = sample_ensemble(None, {"y": y}, M, base_seed=1000, sample_fn=_toy_sample_fn(1000))
         q.put((rank, out.clone()))
+        done.wait(120)        # the tensor travels as a shared-memory fd that this process serves: stay until it is received
         dist.barrier()
     finally:
         dist.destroy_process_group()
@@ -50,12 +51,13 @@ def test_world2_matches_world1(M):
     ref = sample_ensemble(None, {"y": y}, M, base_seed=1000, sample_fn=_toy_sample_fn(1000))      # world 1
     assert ref.shape == (M,) + LAT
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, done = ctx.Queue(), ctx.Event()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, M, q)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, M, q, done)) for r in range(2)]
     for p in procs:
         p.start()
     got = dict(q.get(timeout=120) for _ in range(2))
+    done.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0

@@ -159,7 +159,7 @@ def _free_port():
     return port
 
 
-def _sync_worker(rank, world, port, q):
+def _sync_worker(rank, world, port, q, done):
     """Rank 0 holds state (as after its updates), rank 1 made none; both call sync().  Then both hold state with different M."""
     import os
     import torch.distributed as dist
@@ -185,6 +185,7 @@ def _sync_worker(rank, world, port, q):
         except ValueError as err:
             second = str(err)
         q.put((rank, first, second))
+        done.wait(120)        # the tensors travel as shared-memory fds that this process serves: stay until they are received
         dist.barrier()
     finally:
         dist.destroy_process_group()
@@ -194,12 +195,13 @@ def test_sync_with_state_on_one_rank():
     """sync() is a collective on every rank: a rank that made no update takes part with a zero state and learns M."""
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, done = ctx.Queue(), ctx.Event()
     port = _free_port()
-    procs = [ctx.Process(target=_sync_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_sync_worker, args=(r, 2, port, q, done)) for r in range(2)]
     for p in procs:
         p.start()
     got = dict((r, (a, b)) for r, a, b in (q.get(timeout=120) for _ in range(2)))
+    done.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0

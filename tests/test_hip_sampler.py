@@ -124,6 +124,59 @@ def test_lanes_do_not_change_results(sampler):
     assert bool(torch.isfinite(outs[2]).all())
 
 
+def test_ancestral_hooks_same_in_every_mode():
+    """Per-step hooks of the ancestral loop (intermediates every log_every_t, callback, img_callback, inpainting mask / x0) force the
+    non-lane path: the single graph, the eager loop and num_streams = 2 give the same intermediates and hook arguments bit for bit."""
+    ldm, cfg, _ = _tiny_ldm("bf16")
+    B = 4
+    zc = seeded_input("dzc4", (B,) + tuple(cfg["input_shape"]), 5).cuda()
+    shape = ldm.get_batch_latent_shape(B)
+    g = torch.Generator().manual_seed(19)
+    tape = [torch.randn(shape, generator=g) for _ in range(5)]
+    x0 = torch.randn(shape, generator=g).cuda()
+    mask = torch.zeros(shape, device="cuda")
+    mask[:, :1] = 1.0
+    runs = {}
+    for name, S, graph in (("graph", 1, True), ("eager", 1, False), ("two streams", 2, True)):
+        ldm.num_streams, ldm.use_hip_graph = S, graph
+        seen = []
+        torch.manual_seed(7)                  # the mask's q_sample draws from the device generator
+        out, inter = ldm.p_sample_loop(cond=zc, shape=shape, timesteps=4, noise_tape=tape, return_intermediates=True, log_every_t=2,
+                                       mask=mask, x0=x0, callback=seen.append, img_callback=lambda img, i: seen.append((i, img.clone())))
+        runs[name] = (out, inter, seen)
+    out, inter, seen = runs["graph"]
+    assert len(inter) == 4 and torch.equal(inter[-1], out)      # x_T, then t = 3 (the first step), 2, 0
+    assert [s for s in seen if isinstance(s, int)] == [3, 2, 1, 0]
+    for name in ("eager", "two streams"):
+        o, i, s = runs[name]
+        assert torch.equal(o, out) and len(i) == len(inter) and all(torch.equal(a, b) for a, b in zip(i, inter)), name
+        assert len(s) == len(seen), name
+        for a, b in zip(s, seen):
+            assert a == b if isinstance(b, int) else (a[0] == b[0] and torch.equal(a[1], b[1])), name
+
+
+def test_ddim_intermediates_same_in_every_mode():
+    """DDIM with return_intermediates: the single graph and the eager loop give the same list bit for bit; its last entry is the
+    two-lane result without intermediates."""
+    ldm, cfg, _ = _tiny_ldm("bf16")
+    B = 4
+    zc = seeded_input("dzc4", (B,) + tuple(cfg["input_shape"]), 5).cuda()
+    shape = ldm.get_batch_latent_shape(B)
+    g = torch.Generator().manual_seed(23)
+    tape = [torch.randn(shape, generator=g) for _ in range(6)]
+    ldm.num_streams = 2
+    lanes = ldm.ddim_sample_loop(zc, shape, ddim_steps=5, eta=1.0, noise_tape=tape)
+    assert 1 in ldm._graphs                   # the second lane's graph: the batch did run as two lanes
+    inters = []
+    for graph in (True, False):
+        ldm.use_hip_graph = graph
+        out, inter = ldm.ddim_sample_loop(zc, shape, ddim_steps=5, eta=1.0, noise_tape=tape, return_intermediates=True)
+        assert len(inter) == 6 and torch.equal(inter[-1], out)
+        inters.append(inter)
+    assert all(torch.equal(a, b) for a, b in zip(*inters))
+    assert torch.equal(inters[0][-1], lanes)
+
+
 def test_graph_tracks_weight_updates():
     ldm, cfg, sd = _tiny_ldm("bf16")
     B = 1

@@ -344,6 +344,27 @@ def test_scale_by_std_registers_the_reference_buffer():
     assert torch.equal(a.get_first_stage_encoding(z), 0.25 * z)
 
 
+def test_ddim_refuses_x0_parameterization():
+    """The DDIM step reads the model output as eps: an "x0" model raises NotImplementedError before any work (no draw, no forward),
+    through ddim_sample_loop and through sample(sampler="ddim")."""
+    import torch
+    from prediff_amd.latent_diffusion import LatentDiffusion
+
+    class NoForward(torch.nn.Module):
+        def forward(self, *a):
+            raise AssertionError("the denoiser must not run")
+
+    ldm = LatentDiffusion(torch_nn_module=NoForward(), layout="NTHWC", data_shape=(2, 8, 8, 1), timesteps=1000, use_ema=False,
+                          latent_shape=(2, 4, 4, 1), parameterization="x0")
+    zc = torch.zeros(2, 3, 4, 4, 1)
+    rng = torch.get_rng_state()
+    with pytest.raises(NotImplementedError, match="x0"):
+        ldm.ddim_sample_loop(zc, ldm.get_batch_latent_shape(2), ddim_steps=5)
+    with pytest.raises(NotImplementedError, match="x0"):
+        ldm.sample(cond=zc, batch_size=2, sampler="ddim", ddim_steps=5, return_decoded=False)
+    assert torch.equal(torch.get_rng_state(), rng)
+
+
 def test_modules_deepcopy_and_pickle():
     """A module that owns a pd_call_opts struct stays deepcopy- / pickle-able (EMA by deepcopy, DDP spawn, torch.save(module)):
     ctypes refuses structures with pointer members, so CallOpts serialises its integer members and drops the profiling pointer."""
