@@ -1,0 +1,297 @@
+// pd_igemm, halo-staged Conv3d 3x3x3: the 256 x 256 x 64 eight-wave kernel of igemm256.hip with the A operand staged ONCE per input frame.
+//
+// igemm256_kernel walks K tap-major and stages a fresh 256 x 64 A tile for every K-tile.  For a stride-1, pad-1, un-upsampled 3x3x3
+// convolution on 16 x 16 frames a 256-row tile IS one output frame, and the A rows of the nine (kh, kw) taps of one (channel chunk,
+// temporal tap) are the same 18 x 18 input pixels (frame + spatial ring) at shifted positions: nine K-tiles staged 9 x 32 KB of A out of
+// one 41.5 KB halo.  This kernel walks K as  channel chunk (64) -> temporal tap kt -> (kh, kw),  stages the halo of a (chunk, kt) group
+// once and reads the A fragments of the nine K-tiles of the group out of it at a row shift of kh * 18 + kw.  DMA pieces per wave and
+// K-tile: 4 (W) + 5.25 / 9 (halo) = 4.6 instead of 8.  The tile, the eight waves, the two-phase MFMA schedule, the wave-row stagger, the W
+// stream (rows, swizzle, two K-tile buffers, issued two K-tiles ahead in phase B) and the epilogue are those of igemm256_kernel<2, 8>.
+//
+// Halo layout in LDS: eight PLANES, one per 16-B k-slot s of the 128-B channel chunk; plane s holds the 16 B of halo row r (= hr * 18 + hc,
+// 324 rows, 336 allocated) at  s * PLANE + r * 16,  PLANE = 336 * 16 = 21 * 256 B.  The fragment read of lane (l16, lg) for row tile i
+// (= image row oh = 8 * wave row + i), tap (kh, kw) and k-step ks is the 16 B at
+//      ((oh + kh) * 18 + kw + l16) * 16  +  (4 ks + lg) * PLANE
+// -- one per-lane base register and a COMPILE-TIME offset per (i, kh, kw, ks): no address arithmetic in the loop.  Banks (ds_read_b128 is
+// served in four groups of 16 lanes, each group holding every l16 once with lg differing between its lanes): PLANE is a multiple of the
+// 256-B bank row, so a lane's four banks are 4 * ((R + l16) mod 16) + 0..3 whatever its lg -- 16 consecutive halo rows R .. R + 15 hit 16
+// different bank quads for EVERY shift R: conflict-free for all nine taps.  (A row-major halo with the (row >> 1) & 7 XOR swizzle of the W
+// tile is conflict-free only for R % 4 == 0: rows r and r + 2 of one aligned group of four collide when they sit on either side of the
+// l16 = 3 | 4 or 11 | 12 boundary of a lane group.)
+// A DMA instruction of a wave fills 64 consecutive 16-B cells of that layout (1 KB; each lane names its own source pixel): a halo is 42
+// pieces, wave w issues pieces w, w + 8, ..., w + 32 and waves 0 / 1 also pieces 40 / 41.  The spatial ring, the 12 spare rows of a plane
+// and (dense loop) out-of-range frames come out of the descriptor's bounds check as zeros.
+//
+// Schedule of K-tile j = 0 .. 8 of group g (k = 9 g + j; halo g in halo buffer g & 1, W tile k in W buffer k & 1):
+//   phase A: fragment reads (W column tiles 0-3, A row tiles 0-3); j = 1 .. 5: one halo piece of group g + 1 (j = 1: first the extra piece)
+//   phase B: A row tiles 4-7; the four W pieces of K-tile k + 2; counted vmcnt: everything but this K-tile's own pieces has landed
+// Hazards: halo buffer (g + 1) & 1 was last read in phase B of the last K-tile of group g - 1 and is refilled from K-tile 1 of group g; its
+// last piece is issued in K-tile 5 and retired by the vmcnt(4) of K-tile 6, every wave passes that wait and two workgroup barriers before
+// any wave reads the buffer.  Waves 0 / 1 issue their extra piece FIRST, so it is older than every piece a counted wait must retire:
+// vmcnt(n) leaves the n YOUNGEST operations in flight, and those are the same for all eight waves.  W: as in igemm256_kernel.
+// A kt whose input frame lies outside the sample is left out as a whole group (A and W): the tile-wide tap skipping of igemm256_kernel;
+// debug_flags bit 8 keeps the dense loop (zero halos streamed, identical bits).
+#include <algorithm>
+#include "common.h"
+#include "igemm_epilogue.h"
+
+namespace PD_NS {
+
+#define BLDS16(rsrc, ldsptr, voff, soff) \
+  __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (__attribute__((address_space(3))) void*)(ldsptr), 16, (voff), (soff), 0, 0)
+#define PD_OOB 0xffffff00u
+#define VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+#define PHASE_SYNC()                   \
+  __builtin_amdgcn_sched_barrier(0);   \
+  __builtin_amdgcn_s_barrier();        \
+  __builtin_amdgcn_sched_barrier(0)
+
+namespace {
+constexpr int FW = 16;                       // frame width = height: a 16-row MFMA tile is one image row, a 256-row tile one frame
+constexpr int HW = FW + 2;                   // halo width
+constexpr int HROWS = HW * HW;               // 324 halo rows
+constexpr int PLROWS = 336;                  // rows allocated per plane: PLANE is a multiple of 256 B and 8 planes are whole 1 KB pieces
+constexpr int PLANE = PLROWS * 16;
+constexpr int HALO = 8 * PLANE;              // 43008 B
+constexpr int NPIECE = HALO / 1024;          // 42
+constexpr int WHT = 128 * 128;               // one W half tile: 128 rows x 128 B
+constexpr int WBUF = 2 * WHT;
+constexpr int W_OFF = 2 * HALO;
+constexpr int HALO_LDS = W_OFF + 2 * WBUF;   // 151552 B
+static_assert(PLANE % 256 == 0 && HALO % 1024 == 0 && PLROWS >= HROWS, "halo plane layout");
+static_assert(HALO_LDS >= 8 * 128 * 32 * 4, "the epilogue stages 128 KB of accumulators in the operand buffers");
+
+struct FragH {
+  op8 v[2];
+};
+}  // namespace
+
+__global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 2, wc = wave & 3;
+
+  // ---- XCD-aware tile id (bijective for any tile count) ----
+  const int tiles_n = (p.N + 255) >> 8;
+  const int tiles_m = p.M >> 8;                      // M = B * To * 256
+  const int nt = tiles_m * tiles_n;
+  int t;
+  {
+    const int bid = blockIdx.x, xcd = bid & 7, q = nt >> 3, r = nt & 7;
+    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  }
+  const int tm = t / tiles_n;                        // the tile's frame: sample * To + ot
+  const int m0 = tm << 8;
+  const int n0 = (t % tiles_n) << 8;
+
+  const auto rA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, p.a_bytes, 0x00020000);
+  const auto rW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, p.w_bytes, 0x00020000);
+
+  // ---- W staging: one DMA instruction covers 64 rows x 128 B; thread -> (row tid/8, 16 B slot tid%8), swizzled source chunk ----
+  const int srow = tid >> 3, spos = tid & 7;
+  const uint32_t w_sel = (uint32_t)(spos ^ ((srow >> 1) & 7)) * 16u;
+  uint32_t woff[2][2];
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int n = n0 + hh * 128 + i * 64 + srow;
+      woff[hh][i] = n < p.N ? ((uint32_t)n * (uint32_t)p.ldw) * 2u + w_sel : PD_OOB;
+    }
+  // ---- halo staging: piece q = wave + 8 n covers cells [64 q, 64 q + 64) of the plane layout; this lane's cell -> (k-slot, halo row) ----
+  uint32_t hoff[6];
+#pragma unroll
+  for (int n = 0; n < 6; ++n) {
+    const int cell = (wave + 8 * n) * 64 + lane;
+    const int s = cell / PLROWS, r = cell - s * PLROWS;
+    const int hr = r / HW, hc = r - hr * HW;
+    const bool ok = cell < 8 * PLROWS && r < HROWS && hr >= 1 && hr <= FW && hc >= 1 && hc <= FW;
+    hoff[n] = ok ? (uint32_t)((hr - 1) * FW + (hc - 1)) * (uint32_t)p.lda * 2u + (uint32_t)s * 16u : PD_OOB;
+  }
+
+  // ---- groups: (channel chunk, kt), kt over the temporal taps whose input frame lies inside the sample ----
+  const int kchunks = p.Cin >> 6;
+  const int ot = tm % p.To;
+  const bool dense = (p.debug_flags & 8) != 0;
+  const int kt_lo = dense ? 0 : max(0, 1 - ot), kt_hi = dense ? 2 : min(2, p.Ti - ot);
+  const int ngroups = (p.debug_flags & 1) ? 0 : kchunks * (kt_hi - kt_lo + 1);   // (bit 1: profiling, epilogue only)
+  const uint32_t frame_b = 256u * (uint32_t)p.lda * 2u;                          // bytes of one input frame
+  const uint32_t w_tap_b = (uint32_t)p.w_tap_stride * 2u;
+
+  // the halo stream runs one group ahead of the MFMAs, the W stream two K-tiles; all wave-uniform scalars
+  int h_c = 0, h_kt = kt_lo, w_c = 0, w_kt = kt_lo;
+  uint32_t w_off = (uint32_t)(kt_lo * 9) * w_tap_b;
+  int h_soff = 0;
+  uint32_t h_mask = 0;
+  char* const h_dst = smem + wave * 1024;            // + piece round * 8 KB + buffer * HALO  (lane * 16 is implicit)
+  char* const w_dst = smem + W_OFF + wave * 1024;    // + half * WHT + i * (64 * 128) + buffer * WBUF
+  auto next_halo = [&]() {                           // source of the halo stream's group, then advance the stream
+    const int it = ot - 1 + h_kt;
+    const bool ok = (unsigned)it < (unsigned)p.Ti;
+    h_soff = __builtin_amdgcn_readfirstlane(ok ? (int)((uint32_t)(tm - 1 + h_kt) * frame_b + (uint32_t)h_c * 128u) : 0);
+    h_mask = ok ? 0u : PD_OOB;
+    if (++h_kt > kt_hi) { h_kt = kt_lo; ++h_c; }
+  };
+  auto issue_h = [&](int n, int buf) { BLDS16(rA, h_dst + buf * HALO + n * 8192, hoff[n] | h_mask, h_soff); };
+  auto next_w_group = [&]() {
+    if (++w_kt > kt_hi) { w_kt = kt_lo; ++w_c; }
+    w_off = (uint32_t)(w_kt * 9) * w_tap_b + (uint32_t)w_c * 128u;
+  };
+  auto issue_w = [&](int buf) {                      // both W halves of the W stream's K-tile, then the next tap of the group
+    const int so = __builtin_amdgcn_readfirstlane((int)w_off);
+    char* dst = w_dst + buf * WBUF;
+    BLDS16(rW, dst, woff[0][0], so);
+    BLDS16(rW, dst + 64 * 128, woff[0][1], so);
+    BLDS16(rW, dst + WHT, woff[1][0], so);
+    BLDS16(rW, dst + WHT + 64 * 128, woff[1][1], so);
+    w_off += w_tap_b;
+  };
+
+  f32x4 acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+
+  const int l16 = lane & 15, lg = lane >> 4;
+  const int swz = (l16 >> 1) & 7;
+  const int a_rd = (wr * (8 * HW) + l16) * 16 + lg * PLANE;                       // + ((i + kh) * 18 + kw) * 16 + ks * 4 * PLANE
+  const int b_rd = W_OFF + (wc >> 1) * WHT + ((wc & 1) * 64 + l16) * 128;         // + tile * (16 * 128); slot ((ks*4 + lg) ^ swz)
+
+  // ---- prologue: the halo of group 0, W of K-tiles 0 and 1 (a group has nine K-tiles: both exist) ----
+  if (ngroups > 0) {
+    next_halo();
+    if (wave < 2) issue_h(5, 0);
+#pragma unroll
+    for (int n = 0; n < 5; ++n) issue_h(n, 0);
+    issue_w(0);
+    issue_w(1);
+    VMCNT(4);
+  }
+  __builtin_amdgcn_s_barrier();
+  if (wr == 1) __builtin_amdgcn_s_barrier();   // wave row 1 runs one barrier behind wave row 0
+  __builtin_amdgcn_sched_barrier(0);
+
+  FragH a[4], b0[2], b1[2];
+#define LOAD_B(f, base) \
+  (f).v[0] = *(const op8*)((base) + ((lg ^ swz) * 16)); (f).v[1] = *(const op8*)((base) + (((4 + lg) ^ swz) * 16))
+#define LOAD_A(f, base) \
+  (f).v[0] = *(const op8*)(base); (f).v[1] = *(const op8*)((base) + 4 * PLANE)
+  // one quadrant: 4 row tiles x 2 column tiles x K = 64 (two k-steps); consecutive MFMAs hit different accumulators
+#define QUAD16(R0, C0, bfrag)                                                                               \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                          \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                           \
+      _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                         \
+        acc[(R0) + i][(C0) + c] = mfma_16x16x32(a[i].v[ks], bfrag[c].v[ks], acc[(R0) + i][(C0) + c]);
+
+  int wcur = 0;
+  // one group of nine K-tiles; has_next (another group follows: its halo and the W tiles of its first two K-tiles are issued here) is a
+  // compile-time flag -- the last group is a second copy of the body, and the steady-state loop carries no test for it
+  auto group = [&](auto has_next_t, int g) {
+    constexpr bool has_next = decltype(has_next_t)::value;
+    const int hnxt = (g & 1) ^ 1;
+    const char* sA = smem + (g & 1) * HALO + a_rd;
+    if (has_next) next_halo();
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+      const int shift = ((j / 3) * HW + (j % 3)) * 16;       // byte offset of tap (kh, kw) inside a plane
+      const char* sB = smem + wcur * WBUF + b_rd;
+      // ---------- phase A: all four W column tiles, A row tiles 0-3; quadrants (A0, W0), (A0, W1); a halo piece of group g + 1 ----------
+#pragma unroll
+      for (int c = 0; c < 2; ++c) { LOAD_B(b0[c], sB + c * (16 * 128)); }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { LOAD_A(a[i], sA + shift + i * (HW * 16)); }
+#pragma unroll
+      for (int c = 0; c < 2; ++c) { LOAD_B(b1[c], sB + (2 + c) * (16 * 128)); }
+      if (j >= 1 && j <= 5 && has_next) {
+        if (j == 1 && wave < 2) issue_h(5, hnxt);
+        issue_h(j - 1, hnxt);
+      }
+      PHASE_SYNC();
+      __builtin_amdgcn_s_setprio(1);
+      QUAD16(0, 0, b0)
+      QUAD16(0, 2, b1)
+      __builtin_amdgcn_s_setprio(0);
+      PHASE_SYNC();
+      // ---------- phase B: A row tiles 4-7; quadrants (A1, W1), (A1, W0); W of K-tile k + 2; wait for K-tile k + 1 ----------
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { LOAD_A(a[i], sA + shift + (4 + i) * (HW * 16)); }
+      if (j <= 6 || has_next) {
+        if (j == 7) next_w_group();
+        issue_w(wcur);
+        if (j >= 1 && j <= 5 && has_next) {
+          VMCNT(5);                                          // this K-tile's halo piece and W pieces may still fly
+        } else {
+          VMCNT(4);
+        }
+      } else {
+        VMCNT(0);
+      }
+      PHASE_SYNC();
+      __builtin_amdgcn_s_setprio(1);
+      QUAD16(4, 2, b1)
+      QUAD16(4, 0, b0)
+      __builtin_amdgcn_s_setprio(0);
+      PHASE_SYNC();
+      wcur ^= 1;
+    }
+  };
+  for (int g = 0; g + 1 < ngroups; ++g) group(std::true_type{}, g);
+  if (ngroups > 0) group(std::false_type{}, ngroups - 1);
+#undef QUAD16
+#undef LOAD_A
+#undef LOAD_B
+  if (wr == 0) __builtin_amdgcn_s_barrier();   // re-join the two wave rows
+  if (p.debug_flags & 2) return;               // (profiling: main loop only, nothing is stored)
+
+  // ---- epilogue: two 32-column slabs per wave (8 waves x 128 x 32 fp32 = 128 KB of the operand buffers) ----
+  float* sC = (float*)smem + wave * (128 * 32);
+  const int m_base = m0 + wr * 128;
+  const int m_end = min(p.M, m_base + 128);
+#pragma unroll
+  for (int js = 0; js < 2; ++js) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sC[(i * 16 + 4 * lg + r) * 32 + c * 16 + l16] = acc[i][js * 2 + c][r];
+    __syncthreads();
+    igemm_epilogue<128, 32>(p, sC, lane, m_base, m_end, n0 + wc * 64 + js * 32, 0);
+  }
+#endif
+}
+
+// true when the halo-staged kernel can run this (already validated) launch: a one-product 16-bit 3x3x3, stride-1, pad-1, un-upsampled
+// Conv3d on 16 x 16 frames (M = B * T * 256: every 256-row tile is one whole frame)
+bool pd_conv3d_halo_supported(const pd_igemm_args& a, int kind) {
+  if (kind != 2 || a.split || a.fp8 || a.w_fold > 0 || a.nbatch > 1) return false;
+  if (a.KT != 3 || a.KH != 3 || a.KW != 3 || a.pt != 1 || a.ph != 1 || a.pw != 1) return false;
+  if (a.st != 1 || a.sh != 1 || a.sw != 1 || a.ut != 1 || a.uh != 1 || a.uw != 1 || a.vT > 0 || a.vH > 0 || a.vW > 0) return false;
+  return a.Hi == FW && a.Wi == FW && a.Ho == FW && a.Wo == FW && a.Ti == a.To;
+}
+
+int pd_conv3d_halo_launch(const pd_igemm_args& a, hipStream_t s) {
+  static bool attr_set_dev[PD_MAX_DEVICES];
+  bool& attr_set = attr_set_dev[pd_cur_device()];
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)conv3d_halo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HALO_LDS);
+    if (e != hipSuccess) {
+      pd_set_error("pd_igemm: hipFuncSetAttribute(%d) failed: %s", HALO_LDS, hipGetErrorString(e));
+      return PD_ERR_LAUNCH;
+    }
+    attr_set = true;
+  }
+  const int tiles = (a.M / 256) * ((a.N + 255) / 256);
+  hipLaunchKernelGGL(conv3d_halo_kernel, dim3(tiles, 1, 1), dim3(512), HALO_LDS, s, a);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
+}  // namespace PD_NS
