@@ -93,11 +93,11 @@ typedef struct pd_igemm_args {
   int32_t rows_per_sample, ld_rowvec, ld_res, res_period, ld_mul, act, ld_out, ld_outb, split;
   float alpha;
   int32_t tile;            /* 0 = auto; 1 = 128x128, 2 = 64x64, 3-6 = pipeline variants of 128x128, 7 = 256x256 (8 waves, taps streamed), 8 / 9 = 128x64 / 64x128,
-                              10 = 256x256 halo-staged Conv3d 3x3x3 (16 x 16 frames, one-product 16-bit operands; else as 7) */
+                              10 / 11 = 256x256 halo-staged Conv3d 3x3x3 (16 x 16 / 8 x 8 frames, one-product 16-bit operands; else as 7) */
   int32_t vec_epilogue;    /* set by the library */
   uint32_t a_bytes, w_bytes; /* set by the library: extent of one A / W batch (buffer-descriptor bounds) */
-  int32_t debug_flags;     /* profiling ablations only: 1 skip main loop, 2 skip stores, 4 skip activation, 8 keep the dense tap loop of the 256 x 256 Conv3d kernels,
-                              16 the automatic choice keeps the tap-streamed 256 x 256 kernel where it would take the halo-staged one, 64 four-phase K-tile (0 in production) */
+  int32_t debug_flags;     /* profiling ablations only: 1 skip main loop, 2 skip stores, 4 skip activation, 8 keep the dense tap loop of the 256 x 256 Conv3d kernels (tile 11 skips nothing: no effect),
+                              16 the automatic choice keeps the tap-streamed 256 x 256 kernel where it would take a halo-staged one (tile 10 or 11), 64 four-phase K-tile (0 in production) */
   int32_t ksplit;          /* set by the library: K-slices of a split-K launch (1 = none) */
   float* splitk_ws;        /* caller workspace for split-K partial sums (fp32, splitk_ws_elems elements) or NULL: without it a launch
                               is never split.  Used for small grids (few trajectories per launch): the K loop of a long-K launch is cut

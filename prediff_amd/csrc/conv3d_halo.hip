@@ -31,6 +31,23 @@
 // vmcnt(n) leaves the n YOUNGEST operations in flight, and those are the same for all eight waves.  W: as in igemm256_kernel.
 // A kt whose input frame lies outside the sample is left out as a whole group (A and W): the tile-wide tap skipping of igemm256_kernel;
 // debug_flags bit 8 keeps the dense loop (zero halos streamed, identical bits).
+//
+// Level 1 (conv3d_halo_kernel<1>, tile 11): 8 x 8 frames.  A 256-row tile is FOUR frame slots (frames 4 tm .. 4 tm + 3 of the batch; T need
+// not be a multiple of 4, so a tile may hold the last frames of one sample and the first of the next), and a group's halo is the four input
+// frames of its kt.  Everything above holds with these differences:
+//  - Halo cell of (frame slot f, halo row hr, halo column hc), hr, hc = 0 .. 9:  base(f) + hr * 9 + hc.  Row pitch 9: column 9 of a row IS
+//    column 0 of the next (both zero); row 9 of a frame runs into row 0 of the next (both zero).  base = 0, 88, 169, 257 (a frame needs 81
+//    cells up to its neighbour and reaches 91): 348 cells, 352 allocated, 44 pieces, waves 0-3 issue a sixth.
+//  - An MFMA row tile is NOT two neighbouring image rows of one frame: at any pitch that leaves room for the zero column, their cells
+//    R .. R + 7 and R + pitch .. R + pitch + 7 share a bank quad.  Row tile i of wave row wr is image row i of frame slots 2 wr and 2 wr + 1:
+//    lane l16 reads pixel (i, l16 & 7) of slot 2 wr + (l16 >> 3), and base(2 wr + 1) - base(2 wr) = 88 = 8 mod 16, so the 16 lanes of a group
+//    hit quads R .. R + 7 and R + 8 .. R + 15: conflict-free for all nine shifts.  The epilogue undoes the permutation when it writes the
+//    accumulators to its LDS slab (MFMA row rho of row tile i -> slab row (rho >> 3) * 64 + i * 8 + (rho & 7)); the slab a wave row hands to
+//    igemm_epilogue is 128 consecutive output rows as before.
+//  - Zero fill is per frame slot: a temporal tap can be in range for one slot and out of range for its neighbour (another sample), so each
+//    staging lane carries its cell's slot and tests it against the group's four-bit validity mask; slots past the last frame (B * T not a
+//    multiple of 4) are never valid, and the epilogue stores no row >= M.
+//  - No group is skipped (all four slots are out of range only when T = 1): debug_flags bit 8 changes nothing.
 #include <algorithm>
 #include "common.h"
 #include "igemm_epilogue.h"
@@ -56,18 +73,42 @@ constexpr int HALO = 8 * PLANE;              // 43008 B
 constexpr int NPIECE = HALO / 1024;          // 42
 constexpr int WHT = 128 * 128;               // one W half tile: 128 rows x 128 B
 constexpr int WBUF = 2 * WHT;
-constexpr int W_OFF = 2 * HALO;
-constexpr int HALO_LDS = W_OFF + 2 * WBUF;   // 151552 B
 static_assert(PLANE % 256 == 0 && HALO % 1024 == 0 && PLROWS >= HROWS, "halo plane layout");
-static_assert(HALO_LDS >= 8 * 128 * 32 * 4, "the epilogue stages 128 KB of accumulators in the operand buffers");
+// level 1 (8 x 8 frames, four frame slots per tile): see "Level 1" in the header
+constexpr int FW1 = 8;
+constexpr int RP1 = 9;                       // row pitch: neighbouring image rows share their zero column
+constexpr int FR1 = 81;                      // RP1 * RP1: a frame whose neighbour shares its zero row
+constexpr int FPAIR1 = 88;                   // cells between the two frames of a wave row: 8 mod 16
+constexpr int WROW1 = 169;                   // FPAIR1 + FR1: cells between the frame pairs of the two wave rows
+constexpr int FREACH1 = 91;                  // cells a frame's fragment reads reach from its base: (FW1 + 1) * RP1 + FW1 + 2
+constexpr int PLROWS1 = 352;
+static_assert(FPAIR1 % 16 == 8 && FPAIR1 >= FR1 && WROW1 + FPAIR1 + FREACH1 <= PLROWS1, "level-1 halo plane layout");
+constexpr int frame_base1(int f) { return (f >> 1) * WROW1 + (f & 1) * FPAIR1; }
+
+template <int L>
+struct Lay {                                 // L = 0: 16 x 16 frames, L = 1: 8 x 8 frames
+  static constexpr int ROWS = L ? PLROWS1 : PLROWS;
+  static constexpr int PLANE = ROWS * 16;
+  static constexpr int HALO = 8 * PLANE;     // 43008 / 45056 B
+  static constexpr int NPIECE = HALO / 1024; // 42 / 44
+  static constexpr int NEXTRA = NPIECE - 40; // waves 0 .. NEXTRA - 1 issue a sixth piece
+  static constexpr int PITCH = L ? RP1 : HW; // halo rows between two image rows
+  static constexpr int W_OFF = 2 * HALO;
+  static constexpr int LDS = W_OFF + 2 * WBUF;   // 151552 / 155648 B
+  static_assert(PLANE % 256 == 0 && HALO % 1024 == 0 && NEXTRA >= 0 && NEXTRA <= 8, "halo plane layout");
+  static_assert(LDS >= 8 * 128 * 32 * 4 && LDS <= 160 * 1024, "the epilogue stages 128 KB of accumulators in the operand buffers; a CU has 160 KB");
+};
 
 struct FragH {
   op8 v[2];
 };
 }  // namespace
 
+template <int L>
 __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int PLROWS = Lay<L>::ROWS, PLANE = Lay<L>::PLANE, HALO = Lay<L>::HALO, NEXTRA = Lay<L>::NEXTRA, PITCH = Lay<L>::PITCH,
+                W_OFF = Lay<L>::W_OFF;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -76,14 +117,14 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
 
   // ---- XCD-aware tile id (bijective for any tile count) ----
   const int tiles_n = (p.N + 255) >> 8;
-  const int tiles_m = p.M >> 8;                      // M = B * To * 256
+  const int tiles_m = L ? (p.M + 255) >> 8 : p.M >> 8;   // level 0: M = B * To * 256, whole tiles; level 1: M = B * To * 64
   const int nt = tiles_m * tiles_n;
   int t;
   {
     const int bid = blockIdx.x, xcd = bid & 7, q = nt >> 3, r = nt & 7;
     t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   }
-  const int tm = t / tiles_n;                        // the tile's frame: sample * To + ot
+  const int tm = t / tiles_n;                        // the tile's frame: sample * To + ot  (level 1: frames 4 tm .. 4 tm + 3)
   const int m0 = tm << 8;
   const int n0 = (t % tiles_n) << 8;
 
@@ -107,35 +148,72 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
   for (int n = 0; n < 6; ++n) {
     const int cell = (wave + 8 * n) * 64 + lane;
     const int s = cell / PLROWS, r = cell - s * PLROWS;
-    const int hr = r / HW, hc = r - hr * HW;
-    const bool ok = cell < 8 * PLROWS && r < HROWS && hr >= 1 && hr <= FW && hc >= 1 && hc <= FW;
-    hoff[n] = ok ? (uint32_t)((hr - 1) * FW + (hc - 1)) * (uint32_t)p.lda * 2u + (uint32_t)s * 16u : PD_OOB;
+    if constexpr (L == 0) {
+      const int hr = r / HW, hc = r - hr * HW;
+      const bool ok = cell < 8 * PLROWS && r < HROWS && hr >= 1 && hr <= FW && hc >= 1 && hc <= FW;
+      hoff[n] = ok ? (uint32_t)((hr - 1) * FW + (hc - 1)) * (uint32_t)p.lda * 2u + (uint32_t)s * 16u : PD_OOB;
+    } else {
+      // level 1: source relative to the tile's first frame, with the cell's frame slot in bits 0-1 (the offset is a multiple of 16);
+      // slot code 4 = never a pixel (zero row / column, pad and spare cells): no bit of the four-bit validity mask
+      hoff[n] = PD_OOB | 4u;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        const int rel = r - frame_base1(f), hr = rel / RP1, hc = rel - hr * RP1;
+        if (cell < 8 * PLROWS && rel >= 0 && rel < FR1 && hr >= 1 && hc >= 1)
+          hoff[n] = ((uint32_t)(f * (FW1 * FW1) + (hr - 1) * FW1 + (hc - 1)) * (uint32_t)p.lda * 2u + (uint32_t)s * 16u) | (uint32_t)f;
+      }
+    }
   }
 
   // ---- groups: (channel chunk, kt), kt over the temporal taps whose input frame lies inside the sample ----
   const int kchunks = p.Cin >> 6;
   const int ot = tm % p.To;
   const bool dense = (p.debug_flags & 8) != 0;
-  const int kt_lo = dense ? 0 : max(0, 1 - ot), kt_hi = dense ? 2 : min(2, p.Ti - ot);
+  const int kt_lo = (dense || L) ? 0 : max(0, 1 - ot), kt_hi = (dense || L) ? 2 : min(2, p.Ti - ot);
   const int ngroups = (p.debug_flags & 1) ? 0 : kchunks * (kt_hi - kt_lo + 1);   // (bit 1: profiling, epilogue only)
-  const uint32_t frame_b = 256u * (uint32_t)p.lda * 2u;                          // bytes of one input frame
+  const uint32_t frame_b = (uint32_t)(L ? FW1 * FW1 : FW * FW) * (uint32_t)p.lda * 2u;   // bytes of one input frame
+  // level 1: bit 4 kt + f = temporal tap kt of frame slot f reads a frame of the slot's own sample (and the slot is below M)
+  uint32_t vm_all = 0;
+  if constexpr (L == 1) {
+    int o = (4 * tm) % p.To;
+    for (int f = 0; f < 4; ++f) {
+      if (4 * tm + f < p.B * p.To)
+        for (int kt = 0; kt < 3; ++kt)
+          if ((unsigned)(o - 1 + kt) < (unsigned)p.Ti) vm_all |= 1u << (4 * kt + f);
+      if (++o == p.To) o = 0;
+    }
+  }
   const uint32_t w_tap_b = (uint32_t)p.w_tap_stride * 2u;
 
   // the halo stream runs one group ahead of the MFMAs, the W stream two K-tiles; all wave-uniform scalars
   int h_c = 0, h_kt = kt_lo, w_c = 0, w_kt = kt_lo;
   uint32_t w_off = (uint32_t)(kt_lo * 9) * w_tap_b;
   int h_soff = 0;
-  uint32_t h_mask = 0;
+  uint32_t h_mask = 0, h_back = 0;
   char* const h_dst = smem + wave * 1024;            // + piece round * 8 KB + buffer * HALO  (lane * 16 is implicit)
   char* const w_dst = smem + W_OFF + wave * 1024;    // + half * WHT + i * (64 * 128) + buffer * WBUF
   auto next_halo = [&]() {                           // source of the halo stream's group, then advance the stream
-    const int it = ot - 1 + h_kt;
-    const bool ok = (unsigned)it < (unsigned)p.Ti;
-    h_soff = __builtin_amdgcn_readfirstlane(ok ? (int)((uint32_t)(tm - 1 + h_kt) * frame_b + (uint32_t)h_c * 128u) : 0);
-    h_mask = ok ? 0u : PD_OOB;
+    if constexpr (L == 0) {
+      const int it = ot - 1 + h_kt;
+      const bool ok = (unsigned)it < (unsigned)p.Ti;
+      h_soff = __builtin_amdgcn_readfirstlane(ok ? (int)((uint32_t)(tm - 1 + h_kt) * frame_b + (uint32_t)h_c * 128u) : 0);
+      h_mask = ok ? 0u : PD_OOB;
+    } else {
+      // slot f reads input frame 4 tm + f - 1 + kt; the scalar offset is never negative: in tile 0, kt = 0, it names frame 0 and the
+      // lanes step one frame back (slot 0 is out of range there, so no lane that loads goes below the buffer)
+      const int fin = 4 * tm - 1 + h_kt, fb = max(fin, 0);
+      h_soff = __builtin_amdgcn_readfirstlane((int)((uint32_t)fb * frame_b + (uint32_t)h_c * 128u));
+      h_back = (uint32_t)(fb - fin) * frame_b;
+      h_mask = (vm_all >> (4 * h_kt)) & 15u;        // the four slots' validity
+    }
     if (++h_kt > kt_hi) { h_kt = kt_lo; ++h_c; }
   };
-  auto issue_h = [&](int n, int buf) { BLDS16(rA, h_dst + buf * HALO + n * 8192, hoff[n] | h_mask, h_soff); };
+  auto issue_h = [&](int n, int buf) {
+    uint32_t v;
+    if constexpr (L == 0) v = hoff[n] | h_mask;
+    else v = ((h_mask >> (hoff[n] & 7u)) & 1u) ? (hoff[n] & ~7u) - h_back : PD_OOB;
+    BLDS16(rA, h_dst + buf * HALO + n * 8192, v, h_soff);
+  };
   auto next_w_group = [&]() {
     if (++w_kt > kt_hi) { w_kt = kt_lo; ++w_c; }
     w_off = (uint32_t)(w_kt * 9) * w_tap_b + (uint32_t)w_c * 128u;
@@ -160,13 +238,14 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
 
   const int l16 = lane & 15, lg = lane >> 4;
   const int swz = (l16 >> 1) & 7;
-  const int a_rd = (wr * (8 * HW) + l16) * 16 + lg * PLANE;                       // + ((i + kh) * 18 + kw) * 16 + ks * 4 * PLANE
+  // + ((i + kh) * PITCH + kw) * 16 + ks * 4 * PLANE.  Level 1: MFMA row l16 of row tile i = pixel (i, l16 & 7) of frame slot 2 wr + (l16 >> 3)
+  const int a_rd = (L ? wr * WROW1 + (l16 >> 3) * FPAIR1 + (l16 & 7) : wr * (8 * HW) + l16) * 16 + lg * PLANE;
   const int b_rd = W_OFF + (wc >> 1) * WHT + ((wc & 1) * 64 + l16) * 128;         // + tile * (16 * 128); slot ((ks*4 + lg) ^ swz)
 
   // ---- prologue: the halo of group 0, W of K-tiles 0 and 1 (a group has nine K-tiles: both exist) ----
   if (ngroups > 0) {
     next_halo();
-    if (wave < 2) issue_h(5, 0);
+    if (wave < NEXTRA) issue_h(5, 0);
 #pragma unroll
     for (int n = 0; n < 5; ++n) issue_h(n, 0);
     issue_w(0);
@@ -199,17 +278,17 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
     if (has_next) next_halo();
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
-      const int shift = ((j / 3) * HW + (j % 3)) * 16;       // byte offset of tap (kh, kw) inside a plane
+      const int shift = ((j / 3) * PITCH + (j % 3)) * 16;    // byte offset of tap (kh, kw) inside a plane
       const char* sB = smem + wcur * WBUF + b_rd;
       // ---------- phase A: all four W column tiles, A row tiles 0-3; quadrants (A0, W0), (A0, W1); a halo piece of group g + 1 ----------
 #pragma unroll
       for (int c = 0; c < 2; ++c) { LOAD_B(b0[c], sB + c * (16 * 128)); }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) { LOAD_A(a[i], sA + shift + i * (HW * 16)); }
+      for (int i = 0; i < 4; ++i) { LOAD_A(a[i], sA + shift + i * (PITCH * 16)); }
 #pragma unroll
       for (int c = 0; c < 2; ++c) { LOAD_B(b1[c], sB + (2 + c) * (16 * 128)); }
       if (j >= 1 && j <= 5 && has_next) {
-        if (j == 1 && wave < 2) issue_h(5, hnxt);
+        if (j == 1 && wave < NEXTRA) issue_h(5, hnxt);
         issue_h(j - 1, hnxt);
       }
       PHASE_SYNC();
@@ -220,7 +299,7 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
       PHASE_SYNC();
       // ---------- phase B: A row tiles 4-7; quadrants (A1, W1), (A1, W0); W of K-tile k + 2; wait for K-tile k + 1 ----------
 #pragma unroll
-      for (int i = 0; i < 4; ++i) { LOAD_A(a[i], sA + shift + (4 + i) * (HW * 16)); }
+      for (int i = 0; i < 4; ++i) { LOAD_A(a[i], sA + shift + (4 + i) * (PITCH * 16)); }
       if (j <= 6 || has_next) {
         if (j == 7) next_w_group();
         issue_w(wcur);
@@ -253,6 +332,8 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
   float* sC = (float*)smem + wave * (128 * 32);
   const int m_base = m0 + wr * 128;
   const int m_end = min(p.M, m_base + 128);
+  // accumulator register r of row tile i is MFMA row 4 lg + r; level 1: frame slot (4 lg + r) >> 3 of the wave row, pixel (i, (4 lg + r) & 7)
+  const int c_row = L ? (lg >> 1) * 64 + (lg & 1) * 4 : 4 * lg;
 #pragma unroll
   for (int js = 0; js < 2; ++js) {
     __syncthreads();
@@ -261,37 +342,44 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
 #pragma unroll
       for (int c = 0; c < 2; ++c)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sC[(i * 16 + 4 * lg + r) * 32 + c * 16 + l16] = acc[i][js * 2 + c][r];
+        for (int r = 0; r < 4; ++r) sC[(c_row + i * (L ? 8 : 16) + r) * 32 + c * 16 + l16] = acc[i][js * 2 + c][r];
     __syncthreads();
     igemm_epilogue<128, 32>(p, sC, lane, m_base, m_end, n0 + wc * 64 + js * 32, 0);
   }
 #endif
 }
 
-// true when the halo-staged kernel can run this (already validated) launch: a one-product 16-bit 3x3x3, stride-1, pad-1, un-upsampled
-// Conv3d on 16 x 16 frames (M = B * T * 256: every 256-row tile is one whole frame)
-bool pd_conv3d_halo_supported(const pd_igemm_args& a, int kind) {
+// true when the halo-staged kernel of this level can run the (already validated) launch: a one-product 16-bit 3x3x3, stride-1, pad-1,
+// un-upsampled Conv3d on 16 x 16 frames (level 0; M = B * T * 256: every 256-row tile is one whole frame) or on 8 x 8 frames (level 1;
+// M = B * T * 64: a tile is four frame slots, and a B * T that is no multiple of 4 is handled -- the slots past the last frame stage zeros
+// and the epilogue stores no row >= M)
+bool pd_conv3d_halo_supported(const pd_igemm_args& a, int kind, int level) {
   if (kind != 2 || a.split || a.fp8 || a.w_fold > 0 || a.nbatch > 1) return false;
   if (a.KT != 3 || a.KH != 3 || a.KW != 3 || a.pt != 1 || a.ph != 1 || a.pw != 1) return false;
   if (a.st != 1 || a.sh != 1 || a.sw != 1 || a.ut != 1 || a.uh != 1 || a.uw != 1 || a.vT > 0 || a.vH > 0 || a.vW > 0) return false;
-  return a.Hi == FW && a.Wi == FW && a.Ho == FW && a.Wo == FW && a.Ti == a.To;
+  const int fw = level ? FW1 : FW;
+  return a.Hi == fw && a.Wi == fw && a.Ho == fw && a.Wo == fw && a.Ti == a.To;
 }
 
-int pd_conv3d_halo_launch(const pd_igemm_args& a, hipStream_t s) {
+template <int L>
+static int launch_halo(const pd_igemm_args& a, hipStream_t s) {
+  constexpr int LDS = Lay<L>::LDS;
   static bool attr_set_dev[PD_MAX_DEVICES];
   bool& attr_set = attr_set_dev[pd_cur_device()];
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3d_halo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HALO_LDS);
+    hipError_t e = hipFuncSetAttribute((const void*)conv3d_halo_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     if (e != hipSuccess) {
-      pd_set_error("pd_igemm: hipFuncSetAttribute(%d) failed: %s", HALO_LDS, hipGetErrorString(e));
+      pd_set_error("pd_igemm: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
       return PD_ERR_LAUNCH;
     }
     attr_set = true;
   }
-  const int tiles = (a.M / 256) * ((a.N + 255) / 256);
-  hipLaunchKernelGGL(conv3d_halo_kernel, dim3(tiles, 1, 1), dim3(512), HALO_LDS, s, a);
+  const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
+  hipLaunchKernelGGL(conv3d_halo_kernel<L>, dim3(tiles, 1, 1), dim3(512), LDS, s, a);
   PD_CHECK_LAUNCH();
   return PD_OK;
 }
+
+int pd_conv3d_halo_launch(const pd_igemm_args& a, int level, hipStream_t s) { return level ? launch_halo<1>(a, s) : launch_halo<0>(a, s); }
 
 }  // namespace PD_NS

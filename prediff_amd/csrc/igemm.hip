@@ -258,7 +258,8 @@ static int launch_igemm(const pd_igemm_args& a, hipStream_t s) {
 
 // Tile / pipeline configurations (a.tile): 1 = 128x128, BK 64, 2-stage (2 workgroups/CU);  2 = 64x64, BK 64, 2-stage;  8 / 9 = 128x64 / 64x128;
 // 3 = 128x128, BK 32, 4-stage ring (2 workgroups/CU, 3 K-steps in flight);  4 = 128x128, BK 64, 3-stage (1 workgroup/CU);
-// 7 = 256x256 eight waves (igemm256.hip), 10 = its halo-staged Conv3d form (conv3d_halo.hip); both fall back when the launch is not theirs.
+// 7 = 256x256 eight waves (igemm256.hip), 10 / 11 = its halo-staged Conv3d forms for 16 x 16 / 8 x 8 frames (conv3d_halo.hip); all three fall
+// back when the launch is not theirs (10 and 11 to 7, and never to each other: the summation orders differ).
 template <bool SPLIT, int KIND>
 static int dispatch_igemm(const pd_igemm_args& a, int tile, hipStream_t s) {
   switch (tile) {
@@ -281,9 +282,10 @@ int pd_igemm256_launch(const pd_igemm_args& a, int kind, hipStream_t s);
 int pd_igemm256_ksplit(const pd_igemm_args& a, int kind);
 int pd_igemm256_launch_splitk(const pd_igemm_args& a, int kind, hipStream_t s);
 
-// conv3d_halo.hip: the 256 x 256 kernel with the A operand of a 3x3x3 Conv3d on 16 x 16 frames staged once per input frame (tile 10)
-bool pd_conv3d_halo_supported(const pd_igemm_args& a, int kind);
-int pd_conv3d_halo_launch(const pd_igemm_args& a, hipStream_t s);
+// conv3d_halo.hip: the 256 x 256 kernel with the A operand of a 3x3x3 Conv3d staged once per input frame; level 0 = 16 x 16 frames (tile 10),
+// level 1 = 8 x 8 frames (tile 11)
+bool pd_conv3d_halo_supported(const pd_igemm_args& a, int kind, int level);
+int pd_conv3d_halo_launch(const pd_igemm_args& a, int level, hipStream_t s);
 
 #if !PD_IS_F16
 extern "C" int pd_f16_igemm(const pd_igemm_args*, pd_stream_t);
@@ -380,12 +382,13 @@ extern "C" int PD_ENTRY(igemm)(const pd_igemm_args* pa, pd_stream_t stream) {
       // (the hi/lo form of the 128 x 128 kernel holds 128 KB of LDS: ONE workgroup per CU, a round is 256 tiles)
       const int64_t r128 = a.split ? (t128 + ncu - 1) / ncu : (t128 + 2 * ncu - 1) / (2 * ncu), r256 = (t256 + ncu - 1) / ncu;
       if (a.split ? r256 * 11 <= r128 * 5 : r256 * 33 <= r128 * 20) tile = 7;
-      // ... and its halo-staged form where the launch is one it runs (debug_flags bit 16: keep the tap-streamed kernel, for A/B runs)
-      if (tile == 7 && !(a.debug_flags & 16) && pd_conv3d_halo_supported(a, kind)) tile = 10;
+      // ... and a halo-staged form where the launch is one it runs (debug_flags bit 16: keep the tap-streamed kernel, for A/B runs)
+      if (tile == 7 && !(a.debug_flags & 16))
+        tile = pd_conv3d_halo_supported(a, kind, 0) ? 10 : pd_conv3d_halo_supported(a, kind, 1) ? 11 : 7;
     }
   }
-  if (tile == 10) {
-    if (pd_conv3d_halo_supported(a, kind)) return pd_conv3d_halo_launch(a, s);
+  if (tile == 10 || tile == 11) {
+    if (pd_conv3d_halo_supported(a, kind, tile - 10)) return pd_conv3d_halo_launch(a, tile - 10, s);
     tile = 7;
   }
   if (a.split && tile == 4) tile = 1;   // 3 x 64 KB stages do not fit
