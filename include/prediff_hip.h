@@ -371,6 +371,20 @@ int pd_ensemble_score_update(const float* ens, const float* target, const float*
                              const int64_t* sizes, const int64_t* ens_strides, const int64_t* target_strides, int pool, int keep_seq,
                              long long* n_valid, long long* brier, double* sums, double* ws, int64_t ws_doubles, pd_stream_t stream);
 
+/* Frame scores of test_step (train_sevirlr_prediff.py:937-965: torchmetrics' MeanSquaredError, MeanAbsoluteError and the default
+ * StructuralSimilarityIndexMeasure): pred holds M members of target's shape (1 <= M <= 512), both fp32, read in place.  Per step t (t = 0
+ * unless keep_seq), in fp64 and in a fixed order (bit-reproducible): sums[0][t] += sum (p - t)^2, sums[1][t] += sum |p - t|,
+ * sums[2][t] += sum over the (member, n) frames of the frame's SSIM -- 11 x 11 Gaussian window (sigma 1.5), c1 = (0.01 R)^2,
+ * c2 = (0.03 R)^2, variances clamped at 0, mean over the C (H - 10)(W - 10) windows inside the frame; counts[0][t] += elements,
+ * counts[1][t] += frames (int64).  No NaN masking.  R = data_range, or, when range_buf (device, 2 floats) is not NULL, the call first
+ * writes [max - min of pred, max - min of target] there and uses R = the larger of the two (NaN if either tensor holds one).
+ * sizes: host int64[5] = N, T, H, W, C (H, W >= 11, else PD_ERR_ARG); pred_strides: host int64[6] = member, N, T, H, W, C element
+ * strides; target_strides: host int64[5].  ws: device workspace of pd_frame_score_ws_doubles(M, sizes) doubles (-1: unsupported). */
+int64_t pd_frame_score_ws_doubles(int M, const int64_t* sizes);
+int pd_frame_score_update(const float* pred, const float* target, int M, const int64_t* sizes, const int64_t* pred_strides,
+                          const int64_t* target_strides, float data_range, float* range_buf, int keep_seq, double* sums,
+                          long long* counts, double* ws, int64_t ws_doubles, pd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,9 @@ _PROTOS = {
     "pd_ensemble_score_ws_doubles": (C.c_int64, [C.c_int, C.c_void_p, C.c_int]),
     "pd_ensemble_score_update": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int]
                                  + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+    "pd_frame_score_ws_doubles": (C.c_int64, [C.c_int, C.c_void_p]),
+    "pd_frame_score_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_int]
+                              + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -456,6 +459,18 @@ def ensemble_score_update(ens, target, thresholds, divisor, M, sizes, ens_stride
     _check(lib().pd_ensemble_score_update(ptr(ens), ptr(target), ptr(thresholds), thresholds.numel(), divisor, int(M), _i64(sizes),
                                           _i64(ens_strides), _i64(target_strides), int(pool), 1 if keep_seq else 0, ptr(n_valid), ptr(brier),
                                           ptr(sums), ptr(ws), ws.numel(), stream_ptr()), "pd_ensemble_score_update")
+
+
+def frame_score_ws_doubles(M, sizes):
+    return int(lib().pd_frame_score_ws_doubles(int(M), _i64(sizes)))
+
+
+def frame_score_update(pred, target, M, sizes, pred_strides, target_strides, data_range, range_buf, keep_seq, sums, counts, ws):
+    """pred_strides: member stride followed by the (N, T, H, W, C) strides; sums fp64 [3, T'], counts int64 [2, T'].  range_buf: None
+    (data_range is used) or a 2-float device tensor the call fills with the value ranges of pred and target and reads its range from."""
+    _check(lib().pd_frame_score_update(ptr(pred), ptr(target), int(M), _i64(sizes), _i64(pred_strides), _i64(target_strides),
+                                       float(data_range), ptr(range_buf), 1 if keep_seq else 0, ptr(sums), ptr(counts), ptr(ws),
+                                       ws.numel(), stream_ptr()), "pd_frame_score_update")
 
 
 def attn_block_fused_supported(Cn, heads, vol):

@@ -123,11 +123,14 @@ def split_sequence(seq: torch.Tensor, in_len: int, out_len: int):
 
 @torch.no_grad()
 def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int = 0, rank: int = 0, npy_dir: Optional[str] = None,
-                     score=None, aligned_score=None, ensemble_score=None, aligned_ensemble_score=None, **sample_kwargs):
+                     score=None, aligned_score=None, ensemble_score=None, aligned_ensemble_score=None, frame_score=None,
+                     aligned_frame_score=None, **sample_kwargs):
     """The sampling part of test_step (train_sevirlr_prediff.py:905-979) for one batch of sequences (B, in_len+out_len, H, W, C).
 
     ensemble_score / aligned_ensemble_score (ensemble_score.SEVIREnsembleScore, layout of the sequences; not in the reference): after the
-    loop, updated once with the stacked samples, M = num_samples_per_context members of each of the B contexts."""
+    loop, updated once with the stacked samples, M = num_samples_per_context members of each of the B contexts.
+    frame_score / aligned_frame_score (frame_score.SEVIRFrameScore: the MSE / MAE / SSIM of test_step, :937-965): updated with every
+    sample where score / aligned_score are."""
     import numpy as np
     from .alignment import get_alignment_kwargs_avg_x
     lay, ev = cfg["layout"], cfg["eval"]
@@ -143,6 +146,8 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
                 np.save(os.path.join(npy_dir, f"batch{batch_idx}_rank{rank}_sample{i}_aligned.npy"), pred.float().cpu().numpy())
             if aligned_score is not None:
                 aligned_score.update(pred.float(), tgt)
+            if aligned_frame_score is not None:
+                aligned_frame_score.update(pred.float(), tgt)
             out["aligned_pred"].append(pred)
         if ev.get("eval_unaligned", True):
             pred = ldm.sample(cond={"y": ctx}, batch_size=B, **sample_kwargs).contiguous()
@@ -150,6 +155,8 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
                 np.save(os.path.join(npy_dir, f"batch{batch_idx}_rank{rank}_sample{i}.npy"), pred.float().cpu().numpy())
             if score is not None:
                 score.update(pred.float(), tgt)
+            if frame_score is not None:
+                frame_score.update(pred.float(), tgt)
             out["pred"].append(pred)
     if ensemble_score is not None and out["pred"]:
         ensemble_score.update(torch.stack(out["pred"]).float(), tgt)
