@@ -274,6 +274,19 @@ int pd_ddim_step(const float* zt, const float* eps, const float* noise, const fl
  *   gives pd_ddim_step's result bit for bit.  coef4 (B,4) fp32 per sample: [a_t, a_prev, sigma, gamma]; shift: fp32 like zt. */
 int pd_ddim_step_guided(const float* zt, const float* eps, const float* noise, const float* shift, const float* coef4, float* out, int B, int64_t per_sample, pd_stream_t stream);
 
+/* DPM-Solver++(2M) step, data prediction (no reference implementation): per sample, with the row [a_t, c_x, c_d, w] of
+ *   coef4 (B,4) fp32 (schedule.make_dpmpp_2m_coefficients),
+ *   x0 = (z - sqrt(1-a_t) eps)/sqrt(a_t) ; D = w != 0 ? x0 + w (x0 - hist) : x0 ; out = c_x z + c_d D ; hist <- x0.
+ *   hist: fp32 like zt, the previous step's x0, updated in place; it is not read where w == 0 (first step: it may hold anything, NaN included).
+ *   out must not alias zt, eps or hist. */
+int pd_dpmpp_2m_step(const float* zt, const float* eps, float* hist, const float* coef4, float* out, int B, int64_t per_sample,
+                     pd_stream_t stream);
+
+/* Knowledge-alignment guided form: out = <pd_dpmpp_2m_step> - gamma * shift, the subtraction last, so a zero shift gives pd_dpmpp_2m_step's
+ *   result bit for bit.  coef5 (B,5) fp32 per sample: [a_t, c_x, c_d, w, gamma]; shift: fp32 like zt. */
+int pd_dpmpp_2m_step_guided(const float* zt, const float* eps, float* hist, const float* shift, const float* coef5, float* out, int B,
+                            int64_t per_sample, pd_stream_t stream);
+
 /* Layout glue for the frame-wise VAE: fp32 NCHW <-> channels-last NHWC (taming/autoencoder_kl.py:80-113 callers,
  * latent_diffusion.py:361-380,423-432). */
 int pd_nchw_to_nhwc(const float* x, float* out, int N, int C, int HW, int ld_out, pd_stream_t stream);

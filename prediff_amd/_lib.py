@@ -133,6 +133,8 @@ _PROTOS = {
     "pd_ddpm_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
     "pd_ddim_step": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_ddim_step_guided": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_dpmpp_2m_step": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_dpmpp_2m_step_guided": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -423,6 +425,28 @@ def ddim_step_guided(zt, eps, noise, shift, coef4, out, B, per_sample):
             raise PrediffHipError(f"ddim_step_guided: {name} must be a contiguous fp32 tensor of >= {need} elements")
     _check(lib().pd_ddim_step_guided(ptr(zt), ptr(eps), ptr(noise), ptr(shift), ptr(coef4), ptr(out), B, per_sample, stream_ptr()),
            "pd_ddim_step_guided")
+
+
+def _check_step_operands(fn, operands):
+    for name, x, need in operands:
+        if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.numel() < need:
+            raise PrediffHipError(f"{fn}: {name} must be a contiguous fp32 device tensor of >= {need} elements")
+
+
+def dpmpp_2m_step(zt, eps, hist, coef4, out, B, per_sample):
+    """One DPM-Solver++(2M) step (coef4 rows: a_t, c_x, c_d, w); `hist` (the previous x0) is updated in place."""
+    n = B * per_sample
+    _check_step_operands("dpmpp_2m_step", (("zt", zt, n), ("eps", eps, n), ("hist", hist, n), ("coef4", coef4, 4 * B), ("out", out, n)))
+    _check(lib().pd_dpmpp_2m_step(ptr(zt), ptr(eps), ptr(hist), ptr(coef4), ptr(out), B, per_sample, stream_ptr()), "pd_dpmpp_2m_step")
+
+
+def dpmpp_2m_step_guided(zt, eps, hist, shift, coef5, out, B, per_sample):
+    """pd_dpmpp_2m_step minus gamma * shift (coef5 rows: a_t, c_x, c_d, w, gamma)."""
+    n = B * per_sample
+    _check_step_operands("dpmpp_2m_step_guided", (("zt", zt, n), ("eps", eps, n), ("hist", hist, n), ("shift", shift, n),
+                                                  ("coef5", coef5, 5 * B), ("out", out, n)))
+    _check(lib().pd_dpmpp_2m_step_guided(ptr(zt), ptr(eps), ptr(hist), ptr(shift), ptr(coef5), ptr(out), B, per_sample, stream_ptr()),
+           "pd_dpmpp_2m_step_guided")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):

@@ -190,6 +190,50 @@ extern "C" int pd_ddim_step_guided(const float* zt, const float* eps, const floa
   return PD_OK;
 }
 
+// ---- DPM-Solver++(2M) step, data prediction (no reference implementation; DESIGN.md §7, schedule.make_dpmpp_2m_coefficients) ----
+// Coefficient rows (a_t, c_x, c_d, w[, gamma]) per sample.  `hist` holds the previous step's x0 and is overwritten in place with this
+// step's (every element is read, then written, by the one thread that owns it).  w is per sample, so the `w != 0` test is wave-uniform;
+// with w == 0 (the first step, the lower-order final step) hist is NOT read: a captured graph's history buffer holds stale or
+// uninitialised data there, and 0 * NaN must not reach the output.  GUIDED: as ddim_step_kernel, `- gamma * shift` last.
+template <bool GUIDED, typename... Shift>
+__global__ void __launch_bounds__(256) dpmpp_2m_step_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
+                                                            float* __restrict__ hist, const float* __restrict__ coef,
+                                                            float* __restrict__ out, int64_t per, const Shift* __restrict__... shift) {
+  static_assert(sizeof...(Shift) == (GUIDED ? 1 : 0), "the guided step takes one shift pointer, the un-guided none");
+  constexpr int NC = GUIDED ? 5 : 4;
+  const int b = blockIdx.y;
+  const float a_t = coef[b * NC], c_x = coef[b * NC + 1], c_d = coef[b * NC + 2], w = coef[b * NC + 3];
+  const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t);
+  const bool second_order = w != 0.f;
+  const int64_t base = (int64_t)b * per;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
+    const float z = zt[base + i];
+    const float z0 = fmaf(-s1, eps[base + i], z) * r;      // explicit FMAs: both instantiations round alike, whatever the contraction pass picks
+    float d = z0;
+    if (second_order) d = fmaf(w, z0 - hist[base + i], z0);
+    float v = fmaf(c_d, d, c_x * z);
+    if constexpr (GUIDED) v = v - coef[b * NC + 4] * first_of(shift...)[base + i];
+    out[base + i] = v;
+    hist[base + i] = z0;
+  }
+}
+extern "C" int pd_dpmpp_2m_step(const float* zt, const float* eps, float* hist, const float* coef4, float* out, int B, int64_t per_sample,
+                                pd_stream_t stream) {
+  PD_CHECK_ARG(zt && eps && hist && coef4 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_step: bad args");
+  hipLaunchKernelGGL(dpmpp_2m_step_kernel<false>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, hist, coef4, out,
+                     per_sample);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+extern "C" int pd_dpmpp_2m_step_guided(const float* zt, const float* eps, float* hist, const float* shift, const float* coef5, float* out,
+                                       int B, int64_t per_sample, pd_stream_t stream) {
+  PD_CHECK_ARG(zt && eps && hist && shift && coef5 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_step_guided: bad args");
+  hipLaunchKernelGGL((dpmpp_2m_step_kernel<true, float>), dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, hist, coef5,
+                     out, per_sample, shift);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
 // ---- NCHW <-> NHWC (fp32) ----
 __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ out, int N, int C, int HW, int ld) {
   const int64_t total = (int64_t)N * HW * ld;

@@ -71,8 +71,11 @@ def all_gather_members(local: torch.Tensor, num_members: int, rank: int, world: 
 def sample_ensemble(ldm, cond, num_members: int, base_seed: int = 0, sampler: str = "ddim", ddim_steps: int = 50, eta: float = 0.0,
                     timesteps: Optional[int] = None, micro_batch: Optional[int] = None, group=None, return_decoded: bool = True,
                     use_alignment: bool = False, alignment_kwargs=None, sample_fn: Optional[Callable] = None,
-                    force_collective: bool = False) -> torch.Tensor:
+                    force_collective: bool = False, steps: Optional[int] = None, discretize: str = "quad",
+                    lower_order_final: Optional[bool] = None) -> torch.Tensor:
     """Draw `num_members` samples for ONE context (cond["y"]: (1, T_in, H, W, C)) across all ranks of `group`.
+    sampler="dpmpp_2m" takes `steps` (default 20), `discretize` and `lower_order_final` (LatentDiffusion.dpmpp_2m_sample_loop); it reads
+    draw 0 of each member's noise only.
 
     Returns (num_members, T_out, H, W, C) on every rank.  `sample_fn(cond_batch, batch, noise_fn)` can replace the call into
     `ldm.sample` (used by the CPU gloo tests of the sharding logic)."""
@@ -102,6 +105,9 @@ def sample_ensemble(ldm, cond, num_members: int, base_seed: int = 0, sampler: st
                   alignment_kwargs=ak)
         if sampler == "ddim":
             out = ldm.sample(cb, sampler="ddim", ddim_steps=ddim_steps, eta=eta, **kw)
+        elif sampler == "dpmpp_2m":
+            out = ldm.sample(cb, sampler="dpmpp_2m", steps=20 if steps is None else steps, discretize=discretize,
+                             lower_order_final=lower_order_final, **kw)
         else:
             out = ldm.sample(cb, timesteps=timesteps, **kw)
         outs.append(out)

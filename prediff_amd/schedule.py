@@ -72,6 +72,57 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=False)
     return sigma, a_t, a_before
 
 
+def _half_logsnr(a):
+    """lambda = log(alpha / sigma) = 0.5 * log(a / (1 - a)) of a cumulative alpha."""
+    a = np.asarray(a, dtype=np.float64)
+    return 0.5 * np.log(a / (1.0 - a))
+
+
+def make_logsnr_timesteps(num_steps, alphacums) -> np.ndarray:
+    """`num_steps` grid points (DDPM indices, ascending, unique, the last one T-1) for the multistep solver: the timesteps nearest in
+    lambda to levels evenly spaced in lambda between training steps T-1 and 0.  Step 0 itself is the last step's target (the
+    convention of make_ddim_sampling_parameters), so it is not a grid point."""
+    lam = _half_logsnr(np.asarray(alphacums, dtype=np.float32).astype(np.float64))       # decreasing in t
+    T, S = lam.shape[0], int(num_steps)
+    if not (1 <= S <= T - 1):
+        raise ValueError(f"num_steps must be in [1, {T - 1}], got {num_steps}")
+    levels = np.linspace(lam[0], lam[T - 1], S + 1)[1:]
+    hi = np.clip(np.searchsorted(-lam, -levels), 1, T - 1)                              # lam[hi - 1] >= level >= lam[hi]
+    steps = np.where(np.abs(lam[hi - 1] - levels) <= np.abs(lam[hi] - levels), hi - 1, hi)
+    for i in range(S - 2, -1, -1):        # a schedule too flat in lambda for the count: the nearest timesteps that are still distinct
+        steps[i] = min(steps[i], steps[i + 1] - 1)
+    steps[0] = max(steps[0], 1)
+    for i in range(1, S):
+        steps[i] = max(steps[i], steps[i - 1] + 1)
+    return steps.astype(np.int64)
+
+
+def make_dpmpp_2m_coefficients(alphacums, timesteps, lower_order_final=None):
+    """DPM-Solver++(2M), data prediction (Lu et al. 2022, arXiv:2211.01095, algorithm 2), on the grid of make_ddim_sampling_parameters:
+    a = alphacums[timesteps[idx]], a_prev = the grid point before it (alphacums[0] for idx = 0).  With alpha = sqrt(a),
+    sigma = sqrt(1 - a), lambda = log(alpha / sigma), the k-th VISITED step (k = 0 is the largest timestep) is
+        h_k = lambda(a_prev) - lambda(a);  x0 = (z - sigma eps) / alpha;  D = x0 + w_k (x0 - x0_prev);  w_k = h_{k-1} / (2 h_k)
+        z_prev = (sigma_prev / sigma) z - alpha_prev expm1(-h_k) D
+    w_k = 0 on the first visited step, and on the last one with `lower_order_final` (default: fewer than 15 visited steps, as in the
+    published solver).  A grid point with a_prev == a (quad's repeated integers, the T-1 clamp) is the identity for an ODE solver
+    (h = 0): it is dropped from the visit list and never enters h_{k-1}.
+    Returns (table, visited): table[k] = (a, c_x, c_d, w_k) with c_x = sigma_prev / sigma and c_d = -alpha_prev expm1(-h_k), fp64
+    from the alphacums as given, rounded to fp32 once; visited[k] = the grid index idx of the k-th visited step."""
+    _, a, a_prev = make_ddim_sampling_parameters(np.asarray(alphacums, dtype=np.float64), timesteps, 0.0)
+    visited = np.asarray([idx for idx in reversed(range(len(a))) if a_prev[idx] != a[idx]], dtype=np.int64)
+    a, a_prev = a[visited], a_prev[visited]
+    h = _half_logsnr(a_prev) - _half_logsnr(a)
+    w = np.zeros_like(h)
+    w[1:] = h[:-1] / (2.0 * h[1:])
+    if lower_order_final is None:
+        lower_order_final = len(visited) < 15
+    if lower_order_final and len(w):
+        w[-1] = 0.0
+    c_x = np.sqrt((1.0 - a_prev) / (1.0 - a))
+    c_d = -np.sqrt(a_prev) * np.expm1(-h)
+    return np.stack([a, c_x, c_d, w], axis=1).astype(np.float32), visited
+
+
 def make_ddim_guidance_coefficients(posterior_log_variance_clipped, ddim_timesteps) -> np.ndarray:
     """gamma per DDIM step of the knowledge-aligned DDIM sampler: step idx moves from t = steps[idx] to the alpha of
     steps[idx-1] and skips the DDPM timesteps J_idx = {steps[idx-1] + 1, ..., steps[idx]} ({0, ..., steps[0]} for idx = 0); it
