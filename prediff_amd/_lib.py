@@ -10,6 +10,8 @@ from typing import Optional
 
 import torch
 
+from .packing import pad64  # noqa: F401  (re-exported: L.pad64)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PD_LIB_PATH: another build of the same library (A/B of compiler flags); the default is the in-tree build
 LIB_PATH = os.environ.get("PD_LIB_PATH") or os.path.join(_HERE, "libprediff_hip.so")
@@ -213,10 +215,6 @@ def _dev(t: torch.Tensor, dtype=None):
     if not t.is_contiguous():
         raise PrediffHipError("expected a contiguous tensor")
     return t
-
-
-def pad64(n: int) -> int:
-    return (n + 63) // 64 * 64
 
 
 # --------------------------------------------------------------------------------------------------

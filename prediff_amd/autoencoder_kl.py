@@ -19,6 +19,7 @@ from torch import nn
 
 from . import _lib as L
 from .distributions import DiagonalGaussianDistribution
+from .engine import Act, HipEngine
 from .packing import pack_conv, pack_linear, pad64
 
 VAE_EPS = 1e-6
@@ -125,7 +126,7 @@ class Decoder(_Holder):
         self.conv_out = nn.Conv2d(block_out_channels[0], out_channels, 3, padding=1)
 
 
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(nn.Module, HipEngine):
     def __init__(self, in_channels: int = 3, out_channels: int = 3, down_block_types: Tuple[str] = ("DownEncoderBlock2D",),
                  up_block_types: Tuple[str] = ("UpDecoderBlock2D",), block_out_channels: Tuple[int] = (64,),
                  layers_per_block: int = 1, act_fn: str = "silu", latent_channels: int = 4, norm_num_groups: int = 32,
@@ -133,18 +134,13 @@ class AutoencoderKL(nn.Module):
         super().__init__()
         if act_fn not in ("silu", "swish"):
             raise NotImplementedError(f"act_fn={act_fn!r}: only SiLU is fused in the GroupNorm kernel")
-        if precision not in ("bf16", "fp16", "fp16x2", "fp16x2_lin", "fp32", "fp8", "fp8_conv"):
-            raise ValueError("precision must be 'bf16', 'fp16', 'fp16x2', 'fp16x2_lin', 'fp32', 'fp8' or 'fp8_conv'")
         if precision in ("fp16x2", "fp16x2_lin"):
             # the denoiser's folded-weight engine (exact weights against the error that ACCUMULATES over the sampling steps); the VAE runs once
             # per sample, its weight rounding does not accumulate: it keeps the one-product fp16 engine
             precision = "fp16"
         # "fp8" is a denoiser option (e4m3 operands for its 3x3x3 convolutions); the VAE has no such launches and runs its bf16 engine.
         # "fp16": the bf16 engine on IEEE-half operands (see CuboidTransformerUNet)
-        self.operand = "fp16" if precision == "fp16" else "bf16"
-        self.opts = L.CallOpts(self.operand)          # per-call options of every launch of this module (nothing is process-global)
-        self.op_dtype = self.opts.dtype
-        self.precision = "bf16" if (precision.startswith("fp8") or precision == "fp16") else precision
+        self._init_engine(precision, ("bf16", "fp16", "fp16x2", "fp16x2_lin", "fp32", "fp8", "fp8_conv"))
         self.precision_name = precision
         self.fuse_resblock = True     # bf16 engine: GroupNorm -> SiLU -> Conv2d 3x3 of the ResBlocks as one launch (csrc/conv2d_gn.hip)
         self.latent_channels, self.norm_num_groups = latent_channels, norm_num_groups
@@ -154,9 +150,8 @@ class AutoencoderKL(nn.Module):
         self.post_quant_conv = nn.Conv2d(latent_channels, latent_channels, 1)
         self.use_slicing = False
         self.requires_grad_(False)
-        self._packed, self._packed_key, self._ws = None, None, {}
 
-    # ------------------------------------------------------------------------------------------------ packing / workspace
+    # ------------------------------------------------------------------------------------------------ packing
     def _pack(self, device):
         split = self.precision == "fp32"
         P = {}
@@ -172,45 +167,13 @@ class AutoencoderKL(nn.Module):
                 P[name + ".beta"] = m.bias.detach().float().contiguous().to(device)
         return P
 
-    def _ensure_packed(self, device):
-        key = (str(device), self.precision, self.operand) + tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if key != self._packed_key:
-            L.lib()
-            self._packed, self._packed_key = self._pack(device), key
-        return self._packed
-
-    def _buf(self, name, shape, dtype, device):
-        key = (name, tuple(shape), dtype, str(device))
-        t = self._ws.get(key)
-        if t is None:
-            t = torch.zeros(shape, dtype=dtype, device=device)
-            self._ws[key] = t
-        return t
-
-    def _bf(self, name, rows, cols, device):
-        if self.precision == "fp32":      # both halves in one allocation (the 256 x 256 hi/lo kernel reads them through one buffer descriptor)
-            both = self._buf(name + ".hilo", (2, rows, cols), torch.bfloat16, device)
-            return both[0], both[1]
-        return self._buf(name, (rows, cols), self.op_dtype, device), None
-
     # ------------------------------------------------------------------------------------------------ primitives
-    def _cast(self, x, rows, C, name, dev):
-        ld = pad64(C)
-        a, alo = self._bf(name, rows, ld, dev)
-        L.cast_rows(x, a, alo, 1, rows, 0, rows, C, C, ld, opts=self.opts)
-        return a, alo, ld
+    def _gn(self, P, name, x, N, S, C, dev, silu=True) -> Act:
+        return self._groupnorm(x, P[name + ".g"], P[name + ".beta"], N, S, C, self.norm_num_groups, "gn.a", dev, VAE_EPS, silu=silu)
 
-    def _gn(self, P, name, x, N, S, C, dev, silu=True):
-        ld = pad64(C)
-        a, alo = self._bf("gn.a", N * S, ld, dev)
-        part = self._buf("gn.part", (N * L.groupnorm_nchunk(S, C) * self.norm_num_groups * 2,), torch.float64, dev)
-        L.groupnorm_silu(x, P[name + ".g"], P[name + ".beta"], part, a, alo, N, S, C, self.norm_num_groups, ld, VAE_EPS, silu=silu, opts=self.opts)
-        return a, alo, ld
-
-    def _conv(self, P, name, a, alo, ld, N, hw, Cout, out, dev, k=3, mode="same", residual=None):
+    def _conv(self, P, name, a: Act, N, hw, Cout, out, dev, k=3, mode="same", residual=None):
         """Conv2d on channels-last rows.  mode: same | down (pad (0,1,0,1), stride 2) | up (nearest x2 then 3x3 pad 1)."""
         H, W = hw
-        w, wlo = P[name + ".w"]
         if k == 1:
             geom, taps, Ho, Wo = None, 1, H, W
         elif mode == "same":
@@ -223,8 +186,7 @@ class AutoencoderKL(nn.Module):
             geom, taps = L.conv_geom(N, (1, H, W), (1, 3, 3), pad=(0, 1, 1), up=(1, 2, 2)), 9
         else:
             raise ValueError(mode)
-        L.igemm(a, w, A_lo=alo, W_lo=wlo, M=N * Ho * Wo, N=Cout, Cin=ld, taps=taps, w_tap_stride=Cout * ld, geom=geom,
-                bias=P[name + ".b"], residual=residual, out_f32=out, opts=self.opts)
+        self._gemm(P, name, a, M=N * Ho * Wo, N=Cout, taps=taps, geom=geom, residual=residual, out_f32=out)
         return Ho, Wo
 
     def _gn_conv(self, P, gn_name, conv_name, x, N, hw, Cin, Cout, out, dev, residual=None):
@@ -241,8 +203,7 @@ class AutoencoderKL(nn.Module):
             L.conv2d_gn_silu(x, stats, P[gn_name + ".g"], P[gn_name + ".beta"], P[conv_name + ".w"][0], P[conv_name + ".b"], residual, out,
                              N, H, W, Cin, Cout, G, opts=self.opts)
             return
-        a, alo, ld = self._gn(P, gn_name, x, N, H * W, Cin, dev)
-        self._conv(P, conv_name, a, alo, ld, N, hw, Cout, out, dev, residual=residual)
+        self._conv(P, conv_name, self._gn(P, gn_name, x, N, H * W, Cin, dev), N, hw, Cout, out, dev, residual=residual)
 
     def _resnet(self, P, name, m: ResnetBlock2D, x, N, hw, dev):
         """ResnetBlock2D.forward, temb=None (taming/resnet.py:454-495).  x: fp32 (N*S, Cin) -> fp32 (N*S, Cout)."""
@@ -254,8 +215,7 @@ class AutoencoderKL(nn.Module):
             self._gn_conv(P, name + ".norm2", name + ".conv2", h, N, hw, Cout, Cout, x, dev, residual=x)
             return x
         out = self._buf(f"res.out{Cout}", (N * S, Cout), torch.float32, dev)
-        xa, xalo, ldx = self._cast(x, N * S, Cin, "sc.a", dev)
-        self._conv(P, name + ".conv_shortcut", xa, xalo, ldx, N, hw, Cout, out, dev, k=1)
+        self._conv(P, name + ".conv_shortcut", self._cast(x, "sc.a", N * S, Cin, dev), N, hw, Cout, out, dev, k=1)
         self._gn_conv(P, name + ".norm2", name + ".conv2", h, N, hw, Cout, Cout, out, dev, residual=out)
         return out
 
@@ -263,13 +223,12 @@ class AutoencoderKL(nn.Module):
         """AttentionBlock.forward (taming/attention.py:136-189): x += proj(softmax(q k^T / sqrt(C)) v)."""
         if S % 64 or C % 64:
             raise NotImplementedError("VAE mid attention needs H*W and C to be multiples of 64")
-        h, hlo, ld = self._gn(P, name + ".group_norm", x, N, S, C, dev, silu=False)
-        split = self.precision == "fp32"
+        gn = self._gn(P, name + ".group_norm", x, N, S, C, dev, silu=False)
+        h, hlo, ld = gn.hi, gn.lo, gn.ld
         q, qlo = self._bf("at.q", N * S, C, dev)
         k, klo = self._bf("at.k", N * S, C, dev)
         for nm, (o, olo) in (("query", (q, qlo)), ("key", (k, klo))):
-            w, wlo = P[f"{name}.{nm}.w"]
-            L.igemm(h, w, A_lo=hlo, W_lo=wlo, M=N * S, N=C, Cin=ld, bias=P[f"{name}.{nm}.b"], out_bf16=o, out_bf16_lo=olo, opts=self.opts)
+            self._gemm(P, f"{name}.{nm}", gn, M=N * S, N=C, out_bf16=o, out_bf16_lo=olo)
         # V^T per frame: vt[c, s] = sum_k Wv[c, k] h[s, k]   (the value bias is added after P V: softmax rows sum to 1)
         vt, vtlo = self._bf("at.vt", N * C, S, dev)
         wv, wvlo = P[name + ".value.w"]
@@ -283,8 +242,7 @@ class AutoencoderKL(nn.Module):
         o, olo = self._bf("at.o", N * S, C, dev)
         L.igemm(p, vt, A_lo=plo, W_lo=vtlo, M=S, N=C, Cin=S, nbatch=N, a_batch_stride=S * S, w_batch_stride=C * S,
                 bias=P[name + ".value.b"], out_bf16=o, out_bf16_lo=olo, outb_batch_stride=S * C, opts=self.opts)
-        wp, wplo = P[name + ".proj_attn.w"]
-        L.igemm(o, wp, A_lo=olo, W_lo=wplo, M=N * S, N=C, Cin=C, bias=P[name + ".proj_attn.b"], residual=x, out_f32=x, opts=self.opts)
+        self._gemm(P, name + ".proj_attn", Act(o, olo, C), M=N * S, N=C, residual=x, out_f32=x)
         return x
 
     def _mid(self, P, name, mid: UNetMidBlock2D, x, N, hw, C, dev):
@@ -312,29 +270,29 @@ class AutoencoderKL(nn.Module):
         P = self._ensure_packed(dev)
         xl, N, C, hw = self._input(x, dev)
         enc = self.encoder
-        a, alo, ld = self._cast(xl, N * hw[0] * hw[1], C, "cast.a", dev)
+        a = self._cast(xl, "cast.a", N * hw[0] * hw[1], C, dev)
         C = enc.conv_in.out_channels
         cur = self._buf("enc.x0", (N * hw[0] * hw[1], C), torch.float32, dev)
-        self._conv(P, "encoder.conv_in", a, alo, ld, N, hw, C, cur, dev)
+        self._conv(P, "encoder.conv_in", a, N, hw, C, cur, dev)
         for b, blk in enumerate(enc.down_blocks):
             for r, rn in enumerate(blk.resnets):
                 cur = self._resnet(P, f"encoder.down_blocks.{b}.resnets.{r}", rn, cur, N, hw, dev)
                 C = rn.out_channels
             if blk.downsamplers is not None:
-                a, alo, ld = self._cast(cur, N * hw[0] * hw[1], C, "cast.a", dev)
+                a = self._cast(cur, "cast.a", N * hw[0] * hw[1], C, dev)
                 Ho, Wo = (hw[0] - 2) // 2 + 1, (hw[1] - 2) // 2 + 1
                 nxt = self._buf(f"enc.ds{b}", (N * Ho * Wo, C), torch.float32, dev)
-                hw = self._conv(P, f"encoder.down_blocks.{b}.downsamplers.0.conv", a, alo, ld, N, hw, C, nxt, dev, mode="down")
+                hw = self._conv(P, f"encoder.down_blocks.{b}.downsamplers.0.conv", a, N, hw, C, nxt, dev, mode="down")
                 cur = nxt
         cur = self._mid(P, "encoder.mid_block", enc.mid_block, cur, N, hw, C, dev)
         S = hw[0] * hw[1]
-        a, alo, ld = self._gn(P, "encoder.conv_norm_out", cur, N, S, C, dev)
+        a = self._gn(P, "encoder.conv_norm_out", cur, N, S, C, dev)
         Cz = enc.conv_out.out_channels
         hz = self._buf("enc.z", (N * S, Cz), torch.float32, dev)
-        self._conv(P, "encoder.conv_out", a, alo, ld, N, hw, Cz, hz, dev)
-        a, alo, ld = self._cast(hz, N * S, Cz, "cast.a", dev)
+        self._conv(P, "encoder.conv_out", a, N, hw, Cz, hz, dev)
+        a = self._cast(hz, "cast.a", N * S, Cz, dev)
         mom = self._buf("enc.mom", (N * S, Cz), torch.float32, dev)
-        self._conv(P, "quant_conv", a, alo, ld, N, hw, Cz, mom, dev, k=1)
+        self._conv(P, "quant_conv", a, N, hw, Cz, mom, dev, k=1)
         out = torch.empty((N, Cz, hw[0], hw[1]), dtype=torch.float32, device=dev)
         L.nhwc_to_nchw(mom, out, N, Cz, S, Cz)
         return DiagonalGaussianDistribution(out)
@@ -351,13 +309,13 @@ class AutoencoderKL(nn.Module):
         zl, N, Cz, hw = self._input(z, dev)
         dec = self.decoder
         S = hw[0] * hw[1]
-        a, alo, ld = self._cast(zl, N * S, Cz, "cast.a", dev)
+        a = self._cast(zl, "cast.a", N * S, Cz, dev)
         zq = self._buf("dec.zq", (N * S, Cz), torch.float32, dev)
-        self._conv(P, "post_quant_conv", a, alo, ld, N, hw, Cz, zq, dev, k=1)
-        a, alo, ld = self._cast(zq, N * S, Cz, "cast.a", dev)
+        self._conv(P, "post_quant_conv", a, N, hw, Cz, zq, dev, k=1)
+        a = self._cast(zq, "cast.a", N * S, Cz, dev)
         C = dec.conv_in.out_channels
         cur = self._buf("dec.x0", (N * S, C), torch.float32, dev)
-        self._conv(P, "decoder.conv_in", a, alo, ld, N, hw, C, cur, dev)
+        self._conv(P, "decoder.conv_in", a, N, hw, C, cur, dev)
         cur = self._mid(P, "decoder.mid_block", dec.mid_block, cur, N, hw, C, dev)
         for b, blk in enumerate(dec.up_blocks):
             for r, rn in enumerate(blk.resnets):
@@ -372,14 +330,14 @@ class AutoencoderKL(nn.Module):
                     L.conv2d_up2(cur, P[uname + ".w"][0], P[uname + ".b"], nxt, N, 2 * hw[0], 2 * hw[1], C, C, opts=self.opts)
                     hw = (2 * hw[0], 2 * hw[1])
                 else:
-                    a, alo, ld = self._cast(cur, N * hw[0] * hw[1], C, "cast.a", dev)
-                    hw = self._conv(P, uname, a, alo, ld, N, hw, C, nxt, dev, mode="up")
+                    a = self._cast(cur, "cast.a", N * hw[0] * hw[1], C, dev)
+                    hw = self._conv(P, uname, a, N, hw, C, nxt, dev, mode="up")
                 cur = nxt
         S = hw[0] * hw[1]
-        a, alo, ld = self._gn(P, "decoder.conv_norm_out", cur, N, S, C, dev)
+        a = self._gn(P, "decoder.conv_norm_out", cur, N, S, C, dev)
         Co = dec.conv_out.out_channels
         y = self._buf("dec.y", (N * S, Co), torch.float32, dev)
-        self._conv(P, "decoder.conv_out", a, alo, ld, N, hw, Co, y, dev)
+        self._conv(P, "decoder.conv_out", a, N, hw, Co, y, dev)
         out = torch.empty((N, Co, hw[0], hw[1]), dtype=torch.float32, device=dev)
         L.nhwc_to_nchw(y, out, N, Co, S, Co)
         return out

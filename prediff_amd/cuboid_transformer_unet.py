@@ -27,6 +27,7 @@ from torch import nn
 
 from . import _lib as L
 from .cuboid_geometry import attention_tables, relative_position_bias, relative_position_index
+from .engine import Act, HipEngine
 from .packing import pack_conv, pack_conv_fp8, pack_linear, pack_linear_fp8, pack_pair_block, pack_pair_ffn_split, pack_pair_vecs, pad64
 from .patterns import CuboidSelfAttentionPatterns
 
@@ -297,7 +298,7 @@ class StackCuboidSelfAttentionBlock(_NoTorchForward):
 # ----------------------------------------------------------------------------------------------------------------------
 # the denoiser
 # ----------------------------------------------------------------------------------------------------------------------
-class CuboidTransformerUNet(nn.Module):
+class CuboidTransformerUNet(nn.Module, HipEngine):
     r"""U-Net style CuboidTransformer that parameterises p(x_{t-1}|x_t); see the module docstring."""
 
     def __init__(self, input_shape, target_shape, base_units=128, block_units=None, scale_alpha=1.0, depth=[4, 4, 4],
@@ -328,12 +329,11 @@ class CuboidTransformerUNet(nn.Module):
             raise NotImplementedError(f"norm_layer={norm_layer!r}")
         if downsample_type != "patch_merge" or upsample_type != "upsample":
             raise NotImplementedError
-        if precision not in ("bf16", "fp16", "fp16x2", "fp16x2_lin", "fp32", "fp8", "fp8_conv"):
-            raise ValueError("precision must be 'bf16' (throughput), 'fp16' (the same engine on IEEE-half operands: TF32-class accuracy at the "
-                             "bf16 rate), 'fp16x2' (IEEE-half activations x hi + lo IEEE-half weights: two MFMA products, inside the 1e-3 bar; "
-                             "'fp16x2_lin': the same with the 3x3x3 convolutions on one product), "
-                             "'fp32' (hi/lo split, fp32-class accuracy), 'fp8_conv' (bf16 engine with e4m3 operands for the 3x3x3 "
-                             "convolutions) or 'fp8' (e4m3 for the convolutions and the K >= 512 token linears)")
+        # precision: "bf16" (throughput), "fp16" (the same engine on IEEE-half operands: TF32-class accuracy at the bf16 rate), "fp16x2" (IEEE-half
+        # activations x hi + lo IEEE-half weights: two MFMA products, inside the 1e-3 bar; "fp16x2_lin": the same with the 3x3x3 convolutions
+        # on one product), "fp32" (hi/lo split, fp32-class accuracy), "fp8_conv" (bf16 engine with e4m3 operands for the 3x3x3 convolutions)
+        # or "fp8" (e4m3 for the convolutions and the K >= 512 token linears)
+        self._init_engine(precision, ("bf16", "fp16", "fp16x2", "fp16x2_lin", "fp32", "fp8", "fp8_conv"))
         # "fp16": every kernel of the "bf16" engine with IEEE half as the 16-bit operand type (the library's pd_f16_* builds): 11-bit
         # significands where bf16 has 8 -- the precision class of the reference's own GPU setting (float32_matmul_precision "high" = TF32,
         # scripts/prediff/sevirlr/prediff_sevirlr_v1.yaml:63) at the bf16 MFMA rate.  Range 65504: the packers saturate; everything that is
@@ -347,11 +347,6 @@ class CuboidTransformerUNet(nn.Module):
         # the per-group sweep on the oracle): their rounding stays, the step costs ~1.25x instead of ~1.75x the fp16 engine's.
         self.w_fold = precision in ("fp16x2", "fp16x2_lin")
         self.w_fold_conv3d = precision == "fp16x2"
-        self.operand = "fp16" if precision in ("fp16", "fp16x2", "fp16x2_lin") else "bf16"
-        # per-call options handed to every launch of this module (operand type + A/B switches: bench.py / scripts set attributes here;
-        # nothing is process-global, two modules in one process do not see each other's settings)
-        self.opts = L.CallOpts(self.operand)
-        self.op_dtype = self.opts.dtype
         # "fp8_conv": the bf16 engine with the TimeEmbedResBlock convolutions (45 % of the FLOPs, the long-K launches) on OCP e4m3
         # operands through the scaled K = 128 MFMA; everything else as in "bf16".  "fp8" (BASELINE config 5's operand type): also the
         # K >= 512 token linears (qkv / proj / FFN of the level >= 1 blocks), their A operands written as e4m3 by LayerNorm, the attention
@@ -360,7 +355,6 @@ class CuboidTransformerUNet(nn.Module):
         self.fp8_conv = precision in ("fp8", "fp8_conv")
         self.fp8_linear = precision == "fp8"
         self.fp8_attn_core = True     # precision="fp8": q k^T and attn v of the un-fused attention layers on the fp8 MFMA (e4m3 q, k, v, P)
-        self.precision = "bf16" if (self.fp8_conv or precision in ("fp16", "fp16x2", "fp16x2_lin")) else precision     # "bf16" = the single-pass 16-bit-operand engine
         self.precision_name = precision
         self.fuse_ffn = True          # bf16 mode: fused LN->FFN kernel where the shape allows (units <= 256)
         self.fuse_attn = True         # bf16 mode: fused LN->QKV->attention->proj kernel (head_dim 64, cuboid volume <= 64)
@@ -499,10 +493,7 @@ class CuboidTransformerUNet(nn.Module):
         self.requires_grad_(False)   # inference engine: no autograd through the HIP kernels
 
         # engine state
-        self._packed = None
-        self._packed_key = None
         self._pack_generation = 0
-        self._ws: Dict = {}
         self._ws_slot = 0             # workspace set in use: concurrent sub-batches (LatentDiffusion lanes, one HIP stream each) get their own
         self._tables_dev: Dict = {}
         self._geom = [[attention_tables(self.mem_shapes[i][:3], cs, sh, st, padding_type)
@@ -547,7 +538,7 @@ class CuboidTransformerUNet(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ packing
     def _params_key(self, device):
-        return (str(device), self.precision, self.operand, self.fp8_conv, self.fp8_linear, self.w_fold, self.w_fold_conv3d) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        return (self.fp8_conv, self.fp8_linear, self.w_fold, self.w_fold_conv3d) + super()._params_key(device)
 
     def _packers(self, P: Dict[str, object], device):
         """The per-module packing functions (writing into P): lin, conv, norm, resblock, stack.  `_pack` runs them over the whole
@@ -665,18 +656,12 @@ class CuboidTransformerUNet(nn.Module):
         lin("final", self.final_proj)
         return P
 
-    def _ensure_packed(self, device):
-        key = self._params_key(device)
-        if key != self._packed_key:
-            L.lib()   # fail loudly before any work if the extension is missing
-            self._packed = self._pack(device)
-            self._packed_key = key
-            self._pack_generation += 1      # HIP graphs captured against the previous operand buffers are stale (LatentDiffusion._graph_step)
-            if device not in self._tables_dev:
-                self._tables_dev[device] = [[dict(tok=g["tok_index"].to(device), mask=(g["mask"].to(device) if g["mask"] is not None else None),
-                                                  tok_out=(g["tok_out"].to(device) if g.get("tok_out") is not None else None))
-                                             for g in lvl] for lvl in self._geom]
-        return self._packed
+    def _after_pack(self, device):
+        self._pack_generation += 1      # HIP graphs captured against the previous operand buffers are stale (LatentDiffusion._graph_step)
+        if device not in self._tables_dev:
+            self._tables_dev[device] = [[dict(tok=g["tok_index"].to(device), mask=(g["mask"].to(device) if g["mask"] is not None else None),
+                                              tok_out=(g["tok_out"].to(device) if g.get("tok_out") is not None else None))
+                                         for g in lvl] for lvl in self._geom]
 
     def pack(self, device=None):
         """Pack the weights now (otherwise done lazily at the first forward and after every weight update)."""
@@ -684,35 +669,11 @@ class CuboidTransformerUNet(nn.Module):
         self._ensure_packed(torch.device(device))
         return self
 
-    # ------------------------------------------------------------------------------------------------ workspace
-    def _buf(self, name, shape, dtype, device):
-        key = (name, tuple(shape), dtype, str(device), self._ws_slot)
-        t = self._ws.get(key)
-        if t is None:
-            t = torch.zeros(shape, dtype=dtype, device=device)
-            self._ws[key] = t
-        return t
-
-    def _bf(self, name, rows, cols, device):
-        """bf16 operand buffer pair (hi, lo-or-None)."""
-        if self.precision == "fp32":      # both halves in one allocation: the 256 x 256 hi/lo kernel reads them through one buffer descriptor
-            both = self._buf(name + ".hilo", (2, rows, cols), torch.bfloat16, device)
-            return both[0], both[1]
-        return self._buf(name, (rows, cols), self.op_dtype, device), None
-
     # ------------------------------------------------------------------------------------------------ building blocks
     FP8_ACT_SCALE = 16.0      # GroupNorm -> SiLU outputs are O(1): x16 keeps |y| < 28 in range and 1e-3 above the subnormals
     FP8_ACT_LOG2 = 4          # the same scale for the LayerNorm / attention-core / FFN-1 outputs of the fp8 linears (2^4)
-
-    def _gn_fp8(self, x, g, beta, B, S, C, G, name, dev, ss=None, scale=None):
-        """GroupNorm -> SiLU -> e4m3 rows (value * scale), the A operand of an fp8 convolution launch."""
-        a8 = self._buf(name + ".f8", (B * S, C), torch.float8_e4m3fn, dev)
-        part = self._buf("gn.part", (B * L.groupnorm_nchunk(S, C) * G * 2,), torch.float64, dev)
-        kw = {}
-        if ss is not None:
-            kw = dict(ss_scale=ss, ss_shift=ss[:, C:], ld_ss=2 * C)
-        L.groupnorm_silu_fp8(x, g, beta, part, a8, B, S, C, G, 1e-5, scale or self.FP8_ACT_SCALE, silu=True, **kw)
-        return a8
+    SPLITK_WS_ELEMS = 16 * 1024 * 1024      # fp32 partial-sum workspace (64 MB per workspace set) for split-K Conv3d launches
+    SPLITK_MAX_BATCH = 16                   # launches of more trajectories fill the CUs with whole tiles: never split
 
     @staticmethod
     def _fp8_act_scale(gamma, beta, ssn):
@@ -721,7 +682,6 @@ class CuboidTransformerUNet(nn.Module):
         soon as a checkpoint has outlier gains: 30x entries in gamma measured 0.40 rel-L2 per forward against 0.043 on unit gains
         (tests/test_hip_unet.py::test_v1_unet_heavy_tailed_weights).  e4m3 is a floating-point format: a smaller scale costs the ordinary
         channels no precision until they reach its subnormals (2^-6 / scale).  Scale-shift norm (the affine map then depends on t): the fixed x16."""
-        import math
         if ssn:
             return CuboidTransformerUNet.FP8_ACT_SCALE
         bound = 8.0 * float(gamma.detach().abs().max()) + float(beta.detach().abs().max())
@@ -729,33 +689,8 @@ class CuboidTransformerUNet(nn.Module):
             return CuboidTransformerUNet.FP8_ACT_SCALE
         return float(2.0 ** max(-8, min(8, math.floor(math.log2(448.0 / bound)))))
 
-    def _gn(self, x, g, beta, B, S, C, G, name, dev, silu=True, ss=None):
-        ld = pad64(C)
-        hi, lo = self._bf(name, B * S, ld, dev)
-        part = self._buf("gn.part", (B * L.groupnorm_nchunk(S, C) * G * 2,), torch.float64, dev)
-        kw = {}
-        if ss is not None:
-            kw = dict(ss_scale=ss, ss_shift=ss[:, C:], ld_ss=2 * C)
-        L.groupnorm_silu(x, g, beta, part, hi, lo, B, S, C, G, ld, 1e-5, silu=silu, **kw, opts=self._opts_for(B))
-        return hi, lo, ld
-
-    def _opts_for(self, B):
-        """The module's call options, or a copy with `small_grid` set for launches of the small-batch mode (split_k: kernels may be chosen
-        by launch size there -- finer GroupNorm chunks).  `self.opts` itself is never mutated per launch (lanes may run from their own
-        host threads with different batch sizes); the copy is rebuilt when a caller changed `self.opts` (bench.py's A/B switches)."""
-        if not self._splitk_mode(B):
-            return self.opts
-        want = self.opts.replace(small_grid=1)
-        cur = getattr(self, "_opts_small", None)
-        if cur is None or cur._state() != want._state() or cur.trace != want.trace:
-            self._opts_small = cur = want
-        return cur
-
     def _splitk_mode(self, B):
         return self.precision == "bf16" and B <= self.SPLITK_MAX_BATCH and self.split_k
-
-    SPLITK_WS_ELEMS = 16 * 1024 * 1024      # fp32 partial-sum workspace (64 MB per workspace set) for split-K Conv3d launches
-    SPLITK_MAX_BATCH = 16                   # launches of more trajectories fill the CUs with whole tiles: never split
 
     def _splitk_ws(self, B, dev):
         """Workspace that lets pd_igemm cut the K loop of the Conv3d launches into slices when a small batch leaves most CUs without
@@ -763,6 +698,45 @@ class CuboidTransformerUNet(nn.Module):
         if not self._splitk_mode(B):
             return None
         return self._buf("splitk.ws", (self.SPLITK_WS_ELEMS,), torch.float32, dev)
+
+    def _opts_for(self, B):
+        """The module's call options, or a copy with `small_grid` set for launches of the small-batch mode (split_k: kernels may be chosen
+        by launch size there -- finer GroupNorm chunks).  `self.opts` itself is never mutated per launch (lanes may run from their own
+        host threads with different batch sizes); the copy is kept until a caller changes `self.opts` (bench.py's A/B switches)."""
+        if not self._splitk_mode(B):
+            return self.opts
+        o = self.opts
+        key = (bytes(o),) + tuple(getattr(o, n) for n in o._HOST_FIELDS)      # every struct member (`trace` included) + the host-side presets
+        cur = getattr(self, "_opts_small", None)
+        if cur is None or cur[0] != key:
+            self._opts_small = cur = (key, o.replace(small_grid=1))
+        return cur[1]
+
+    def _gn_for(self, P, gn, conv, x, B, S, C, G, dev, ss=None) -> Act:
+        """GroupNorm `gn` [-> scale-shift] -> SiLU as the A operand of convolution `conv`: e4m3 rows (value * the layer's activation scale)
+        where the layer has an e4m3 weight record (precision="fp8" / "fp8_conv"), else 16-bit rows."""
+        g, beta = P[gn + ".g"], P[gn + ".beta"]
+        if (conv + ".w8") not in P:
+            return self._groupnorm(x, g, beta, B, S, C, G, "gn.a", dev, 1e-5, ss=ss, opts=self._opts_for(B))
+        scale = P[conv + ".a8s"]
+        a8 = self._buf("gn.a.f8", (B * S, C), torch.float8_e4m3fn, dev)
+        part = self._buf("gn.part", (B * L.groupnorm_nchunk(S, C) * G * 2,), torch.float64, dev)
+        kw = dict(ss_scale=ss, ss_shift=ss[:, C:], ld_ss=2 * C) if ss is not None else {}
+        L.groupnorm_silu_fp8(x, g, beta, part, a8, B, S, C, G, 1e-5, scale, silu=True, **kw)
+        return Act(a8, None, C, scale)
+
+    def _ln(self, P, name, x, rows, C, dev, fp8=False) -> Act:
+        """LayerNorm `name`.ln as a GEMM operand: 16-bit rows, or (fp8) e4m3 rows of value * 2^FP8_ACT_LOG2."""
+        g, beta = P[name + ".ln.g"], P[name + ".ln.beta"]
+        if fp8:
+            a8 = self._buf("ln.a8", (rows, C), torch.float8_e4m3fn, dev)
+            scale = float(2 ** self.FP8_ACT_LOG2)
+            L.layernorm_fp8(x, g, beta, a8, rows, C, C, scale)
+            return Act(a8, None, C, scale)
+        ld = pad64(C)
+        a = self._bf("ln.a", rows, ld, dev)
+        L.layernorm(x, g, beta, *a, rows, C, ld, opts=self.opts)
+        return Act(*a, ld)
 
     def _resblock(self, P, name, m: TimeEmbedResBlock, x, B, thw, emb, dev, out=None):
         """TimeEmbedResBlock.forward (models/time_embed.py:134-169) on channels-last fp32 x (B*S, Cin)."""
@@ -773,50 +747,21 @@ class CuboidTransformerUNet(nn.Module):
         geom = L.conv_geom(B, thw, (3, 3, 3))
         h = self._buf("res.h", (B * S, Cout), torch.float32, dev)
         ssn = m.use_embed and m.use_scale_shift_norm
-        ld1 = pad64(Cin)
-        if (name + ".conv1.w8") in P:       # precision="fp8": e4m3 operands, tensor scales folded into alpha
-            sa = P[name + ".conv1.a8s"]
-            a8 = self._gn_fp8(x, P[name + ".gn1.g"], P[name + ".gn1.beta"], B, S, Cin, m.in_groups, "gn.a", dev, scale=sa)
-            w8, sw = P[name + ".conv1.w8"]
-            L.igemm(a8, w8, M=B * S, N=Cout, Cin=Cin, taps=27, w_tap_stride=Cout * Cin, geom=geom, bias=P[name + ".conv1.b"],
-                    rowvec=(emb if (m.use_embed and not ssn) else None), rows_per_sample=S, out_f32=h,
-                    alpha=1.0 / (sa * sw), fp8=True, splitk_ws=ws, opts=self.opts)
-        else:
-            a1, a1lo, ld1 = self._gn(x, P[name + ".gn1.g"], P[name + ".gn1.beta"], B, S, Cin, m.in_groups, "gn.a", dev)
-            w1, w1lo = P[name + ".conv1.w"]
-            L.igemm(a1, w1, A_lo=a1lo, W_lo=w1lo, M=B * S, N=Cout, Cin=ld1, taps=27, w_tap_stride=Cout * ld1, geom=geom,
-                    bias=P[name + ".conv1.b"], rowvec=(emb if (m.use_embed and not ssn) else None), rows_per_sample=S, out_f32=h,
-                    splitk_ws=ws, opts=self.opts)
-        ldo = pad64(Cout)
-        fp8_2 = (name + ".conv2.w8") in P
-        if fp8_2:
-            sa2 = P[name + ".conv2.a8s"]
-            a28 = self._gn_fp8(h, P[name + ".gn2.g"], P[name + ".gn2.beta"], B, S, Cout, m.out_groups, "gn.a", dev,
-                               ss=(emb if ssn else None), scale=sa2)
-        else:
-            a2, a2lo, _ = self._gn(h, P[name + ".gn2.g"], P[name + ".gn2.beta"], B, S, Cout, m.out_groups, "gn.a", dev,
-                                   ss=(emb if ssn else None))
-            w2, w2lo = P[name + ".conv2.w"]
+        a1 = self._gn_for(P, name + ".gn1", name + ".conv1", x, B, S, Cin, m.in_groups, dev)
+        self._gemm(P, name + ".conv1", a1, M=B * S, N=Cout, taps=27, geom=geom, rowvec=(emb if (m.use_embed and not ssn) else None),
+                   rows_per_sample=S, out_f32=h, splitk_ws=ws)
+        a2 = self._gn_for(P, name + ".gn2", name + ".conv2", h, B, S, Cout, m.out_groups, dev, ss=(emb if ssn else None))
         if out is None:
             out = x if Cin == Cout else self._buf("res.out", (B * S, Cout), torch.float32, dev)
         if isinstance(m.skip_connection, nn.Identity):
             res = x
         else:
             # 1x1x1 (or 3x3x3 when use_conv) skip on the raw input, written to `out`, then accumulated into by conv2
-            xa, xalo = self._bf("skip.a", B * S, ld1, dev)
-            L.cast_rows(x, xa, xalo, B, S, 0, S, Cin, Cin, ld1, opts=self.opts)
-            wsk, wsklo = P[name + ".skip.w"]
             k = m.skip_connection.kernel_size[0]
-            L.igemm(xa, wsk, A_lo=xalo, W_lo=wsklo, M=B * S, N=Cout, Cin=ld1, taps=k ** 3, w_tap_stride=Cout * ld1,
-                    geom=L.conv_geom(B, thw, (k, k, k), pad=(k // 2,) * 3), bias=P[name + ".skip.b"], out_f32=out, opts=self.opts)
+            self._gemm(P, name + ".skip", self._cast(x, "skip.a", S, Cin, dev, samples=B), M=B * S, N=Cout, taps=k ** 3,
+                       geom=L.conv_geom(B, thw, (k, k, k), pad=(k // 2,) * 3), out_f32=out)
             res = out
-        if fp8_2:
-            w8, sw = P[name + ".conv2.w8"]
-            L.igemm(a28, w8, M=B * S, N=Cout, Cin=Cout, taps=27, w_tap_stride=Cout * Cout, geom=geom, bias=P[name + ".conv2.b"],
-                    residual=res, out_f32=out, alpha=1.0 / (sa2 * sw), fp8=True, splitk_ws=ws, opts=self.opts)
-        else:
-            L.igemm(a2, w2, A_lo=a2lo, W_lo=w2lo, M=B * S, N=Cout, Cin=ldo, taps=27, w_tap_stride=Cout * ldo, geom=geom,
-                    bias=P[name + ".conv2.b"], residual=res, out_f32=out, splitk_ws=ws, opts=self.opts)
+        self._gemm(P, name + ".conv2", a2, M=B * S, N=Cout, taps=27, geom=geom, residual=res, out_f32=out, splitk_ws=ws)
         return out
 
     def _patch_merge(self, P, name, dl: PatchMerging3D, x, B, thw, Cp, Cout, ds, out, dev):
@@ -828,8 +773,7 @@ class CuboidTransformerUNet(nn.Module):
         a, alo = self._bf("pm.a", B * So, ldm, dev)
         L.patch_merge_layernorm(x, P[name + ".ln.g"], P[name + ".ln.beta"], a, alo, B, Tp, Hp, Wp, Cp, ds, ldm,
                                 pad_nearest=dl.padding_type == "nearest", opts=self.opts)
-        wr, wrlo = P[name + ".red.w"]
-        L.igemm(a, wr, A_lo=alo, W_lo=wrlo, M=B * So, N=Cout, Cin=ldm, out_f32=out, opts=self.opts)
+        self._gemm(P, name + ".red", Act(a, alo, ldm), M=B * So, N=Cout, out_f32=out)
 
     def _upsample(self, P, name, x, B, thw, Ci, out_hw, Cn, k, res, out, dev):
         """Upsample3DLayer.forward (cuboid_transformer.py:299-373): nearest x2 in (H, W) + Conv2d k x k per frame [+ fp32 residual]."""
@@ -838,13 +782,9 @@ class CuboidTransformerUNet(nn.Module):
         if not (Hi == (Hn + 1) // 2 and Wi == (Wn + 1) // 2):
             raise NotImplementedError("Upsample3DLayer: only x2 nearest up-sampling is implemented")
         Si = Ti * Hi * Wi
-        ldc = pad64(Ci)
-        a, alo = self._bf("up.a", B * Si, ldc, dev)
-        L.cast_rows(x, a, alo, B, Si, 0, Si, Ci, Ci, ldc, opts=self.opts)
+        a = self._cast(x, "up.a", Si, Ci, dev, samples=B)
         geom = L.conv_geom(B * Ti, (1, Hi, Wi), (1, k, k), pad=(0, k // 2, k // 2), up=(1, 2, 2), out_thw=(1, Hn, Wn), virt_thw=(1, Hn, Wn))
-        wu, wulo = P[name + ".conv.w"]
-        L.igemm(a, wu, A_lo=alo, W_lo=wulo, M=B * Ti * Hn * Wn, N=Cn, Cin=ldc, taps=k * k, w_tap_stride=Cn * ldc, geom=geom,
-                bias=P[name + ".conv.b"], residual=res, out_f32=out, opts=self.opts)
+        self._gemm(P, name + ".conv", a, M=B * Ti * Hn * Wn, N=Cn, taps=k * k, geom=geom, residual=res, out_f32=out)
 
     def _attention(self, P, name, at: CuboidSelfAttentionLayer, x, B, S, C, tabs, geo, dev):
         """x += CuboidSelfAttentionLayer(x)  (cuboid_transformer.py:812-966, residual of :1151)."""
@@ -860,57 +800,42 @@ class CuboidTransformerUNet(nn.Module):
                                P[name + ".proj.w"][0], P[name + ".proj.b"], tabs["tok"], P[name + ".bias"], tabs["mask"],
                                B, S, C, at.num_heads, geo["nc"], geo["vol"], float(at.scale), tok_affine=geo.get("affine"), opts=self.opts)
             return
-        if ((name + ".qkv.w8") in P and (name + ".proj.w8") in P and geo["vol"] <= 64 and (C // at.num_heads) % 32 == 0 and ld == C
-                and tabs.get("tok_out") is None):
-            # precision="fp8", long-K level: LayerNorm -> e4m3, QKV on e4m3 operands, q / k / v leave the GEMM as e4m3 too and the core runs
-            # q k^T and attn v on the fp8 MFMA (probabilities as e4m3(P * 256); fp32 scores, softmax, accumulation: BASELINE config 5's
-            # "fp8 MFMA attention", cuboid_transformer.py:849-861,947-952), the core's output -> e4m3, proj on e4m3 operands (+ residual).
-            # Tensor scales (powers of two) ride in alpha.  `fp8_attn_core = False`: bf16 q / k / v and the bf16 core (round 4-5 behaviour).
-            k8 = self.FP8_ACT_LOG2
-            a8 = self._buf("ln.a8", (B * S, C), torch.float8_e4m3fn, dev)
-            L.layernorm_fp8(x, P[name + ".ln.g"], P[name + ".ln.beta"], a8, B * S, C, C, float(2 ** k8))
-            w8, sw = P[name + ".qkv.w8"]
-            o8 = self._buf("attn.o8", (B * S, C), torch.float8_e4m3fn, dev)
-            kw = dict(out_bf16=o8, tok_index=tabs["tok"], bias=P[name + ".bias"], mask=tabs["mask"], B=B, ntok=S, Cn=C, heads=at.num_heads,
-                      nc=geo["nc"], vol=geo["vol"], ld_qkv=3 * C, ld_out=C, scale=float(at.scale), out_fp8_log2=k8, opts=self.opts)
-            if self.fp8_attn_core:
-                qkv8 = self._buf("qkv.f8", (B * S, 3 * C), torch.float8_e4m3fn, dev)
-                L.igemm(a8, w8, M=B * S, N=3 * C, Cin=C, bias=P[name + ".qkv.b"], out_bf16=qkv8, alpha=1.0 / (2 ** k8 * sw), fp8=True,
-                        out_fp8_log2=k8, opts=self.opts)
-                L.cuboid_attention(qkv_bf16=qkv8, qkv_fp8_log2=k8, **kw)
-            else:
-                qkv = self._buf("qkv.bf16", (B * S, 3 * C), torch.bfloat16, dev)
-                L.igemm(a8, w8, M=B * S, N=3 * C, Cin=C, bias=P[name + ".qkv.b"], out_bf16=qkv, alpha=1.0 / (2 ** k8 * sw), fp8=True, opts=self.opts)
-                L.cuboid_attention(qkv_bf16=qkv, **kw)
-            w8, sw = P[name + ".proj.w8"]
-            L.igemm(o8, w8, M=B * S, N=C, Cin=C, bias=P[name + ".proj.b"], residual=x, out_f32=x, alpha=1.0 / (2 ** k8 * sw), fp8=True, opts=self.opts)
-            return
-        a, alo = self._bf("ln.a", B * S, ld, dev)
-        L.layernorm(x, P[name + ".ln.g"], P[name + ".ln.beta"], a, alo, B * S, C, ld, opts=self.opts)
-        wq, wqlo = P[name + ".qkv.w"]
-        fp32 = self.precision == "fp32"
-        o, olo = self._bf("attn.o", B * S, ld, dev)
-        kw = dict(tok_index=tabs["tok"], bias=P[name + ".bias"], mask=tabs["mask"], B=B, ntok=S, Cn=C, heads=at.num_heads,
-                  nc=geo["nc"], vol=geo["vol"], ld_qkv=3 * C, ld_out=ld, scale=float(at.scale), tok_out=tabs.get("tok_out"))
-        need_f32_out = not at.use_final_proj
-        of32 = self._buf("attn.of32", (B * S, ld), torch.float32, dev) if need_f32_out else None
-        if fp32:
-            qkv = self._buf("qkv.f32", (B * S, 3 * C), torch.float32, dev)
-            L.igemm(a, wq, A_lo=alo, W_lo=wqlo, M=B * S, N=3 * C, Cin=ld, bias=P[name + ".qkv.b"], out_f32=qkv, opts=self.opts)
-            L.cuboid_attention(qkv_f32=qkv, out_bf16=o, out_bf16_lo=olo, out_f32=of32, **kw, opts=self.opts)
+        # precision="fp8", long-K level: LayerNorm -> e4m3, QKV on e4m3 operands, q / k / v leave the GEMM as e4m3 too and the core runs
+        # q k^T and attn v on the fp8 MFMA (probabilities as e4m3(P * 256); fp32 scores, softmax, accumulation: BASELINE config 5's
+        # "fp8 MFMA attention", cuboid_transformer.py:849-861,947-952), the core's output -> e4m3, proj on e4m3 operands (+ residual).
+        # Tensor scales (powers of two) ride in alpha.  `fp8_attn_core = False`: bf16 q / k / v and the bf16 core (round 4-5 behaviour).
+        # (a `.proj.w8` record exists only with use_final_proj: the e4m3 form always ends in the proj launch, `of32` is None there)
+        fp8 = ((name + ".qkv.w8") in P and (name + ".proj.w8") in P and geo["vol"] <= 64 and (C // at.num_heads) % 32 == 0 and ld == C
+               and tabs.get("tok_out") is None)
+        k8 = self.FP8_ACT_LOG2 if fp8 else 0
+        rows = B * S
+        a = self._ln(P, name, x, rows, C, dev, fp8=fp8)
+        if fp8:
+            o = Act(self._buf("attn.o8", (rows, C), torch.float8_e4m3fn, dev), None, C, float(2 ** k8))
         else:
-            qkv = self._buf("qkv.bf16", (B * S, 3 * C), self.op_dtype, dev)
-            L.igemm(a, wq, M=B * S, N=3 * C, Cin=ld, bias=P[name + ".qkv.b"], out_bf16=qkv, opts=self.opts)
-            L.cuboid_attention(qkv_bf16=qkv, out_bf16=o, out_f32=of32, **kw, opts=self.opts)
+            o = Act(*self._bf("attn.o", rows, ld, dev), ld)
+        of32 = self._buf("attn.of32", (rows, ld), torch.float32, dev) if not at.use_final_proj else None
+        core = dict(tok_index=tabs["tok"], bias=P[name + ".bias"], mask=tabs["mask"], B=B, ntok=S, Cn=C, heads=at.num_heads, nc=geo["nc"],
+                    vol=geo["vol"], ld_qkv=3 * C, ld_out=ld, scale=float(at.scale), tok_out=tabs.get("tok_out"), out_bf16=o.hi,
+                    out_bf16_lo=o.lo, out_f32=of32, out_fp8_log2=k8, opts=self.opts)
+        if fp8 and self.fp8_attn_core:
+            qkv = self._buf("qkv.f8", (rows, 3 * C), torch.float8_e4m3fn, dev)
+            self._gemm(P, name + ".qkv", a, M=rows, N=3 * C, out_bf16=qkv, out_fp8_log2=k8)
+            L.cuboid_attention(qkv_bf16=qkv, qkv_fp8_log2=k8, **core)
+        elif self.precision == "fp32":
+            qkv = self._buf("qkv.f32", (rows, 3 * C), torch.float32, dev)
+            self._gemm(P, name + ".qkv", a, M=rows, N=3 * C, out_f32=qkv)
+            L.cuboid_attention(qkv_f32=qkv, **core)
+        else:
+            qkv = self._buf("qkv.bf16", (rows, 3 * C), self.op_dtype, dev)
+            self._gemm(P, name + ".qkv", a, M=rows, N=3 * C, out_bf16=qkv)
+            L.cuboid_attention(qkv_bf16=qkv, **core)
         if at.use_final_proj:
-            wp, wplo = P[name + ".proj.w"]
-            L.igemm(o, wp, A_lo=olo, W_lo=wplo, M=B * S, N=C, Cin=ld, bias=P[name + ".proj.b"], residual=x, out_f32=x, opts=self.opts)
+            self._gemm(P, name + ".proj", o, M=rows, N=C, residual=x, out_f32=x)
+        elif ld != C:
+            raise NotImplementedError("use_final_proj=False needs C % 64 == 0")
         else:
-            L.add(x, of32, x, B * S * C) if ld == C else self._raise("use_final_proj=False needs C % 64 == 0")
-
-    @staticmethod
-    def _raise(msg):
-        raise NotImplementedError(msg)
+            L.add(x, of32, x, rows * C)
 
     def _ffn(self, P, name, ff: PositionwiseFFN, x, B, S, C, dev):
         """x = PositionwiseFFN(x), pre-norm, residual inside (cuboid_transformer.py:182-208)."""
@@ -928,33 +853,24 @@ class CuboidTransformerUNet(nn.Module):
             L.ffn_fused(x, x, P[name + ".ln.g"], P[name + ".ln.beta"], P[name + ".fc1.w"][0], P[name + ".fc1.b"], P[name + ".fc2.w"][0],
                         P[name + ".fc2.b"], B * S, C, Hd, act=ff.activation_name, opts=self.opts)
             return
-        if (name + ".fc1.w8") in P and (name + ".fc2.w8") in P and ld == C and ldh == Hd:
-            # precision="fp8", long-K level: LayerNorm -> e4m3 -> FFN-1 (activation -> e4m3 in its epilogue) -> FFN-2 (+ residual)
-            k8 = self.FP8_ACT_LOG2
-            a8 = self._buf("ln.a8", (B * S, C), torch.float8_e4m3fn, dev)
-            L.layernorm_fp8(x, P[name + ".ln.g"], P[name + ".ln.beta"], a8, B * S, C, C, float(2 ** k8))
-            h8 = self._buf("ffn.h8", (B * S, Hd), torch.float8_e4m3fn, dev)
-            w8, sw = P[name + ".fc1.w8"]
-            L.igemm(a8, w8, M=B * S, N=Hd, Cin=C, bias=P[name + ".fc1.b"], act=ff.activation_name, out_bf16=h8, ld_outb=Hd,
-                    alpha=1.0 / (2 ** k8 * sw), fp8=True, out_fp8_log2=k8, opts=self.opts)
-            w8, sw = P[name + ".fc2.w8"]
-            L.igemm(h8, w8, M=B * S, N=C, Cin=Hd, bias=P[name + ".fc2.b"], residual=x, out_f32=x, alpha=1.0 / (2 ** k8 * sw), fp8=True, opts=self.opts)
-            return
-        a, alo = self._bf("ln.a", B * S, ld, dev)
-        L.layernorm(x, P[name + ".ln.g"], P[name + ".ln.beta"], a, alo, B * S, C, ld, opts=self.opts)
-        h, hlo = self._bf("ffn.h", B * S, ldh, dev)
-        w1, w1lo = P[name + ".fc1.w"]
-        if ff.gated:
-            tmp = self._buf("ffn.tmp", (B * S, Hd), torch.float32, dev)
-            L.igemm(a, w1, A_lo=alo, W_lo=w1lo, M=B * S, N=Hd, Cin=ld, bias=P[name + ".fc1.b"], out_f32=tmp, opts=self.opts)
-            wg, wglo = P[name + ".gate.w"]
-            L.igemm(a, wg, A_lo=alo, W_lo=wglo, M=B * S, N=Hd, Cin=ld, bias=P[name + ".gate.b"], act=ff.activation_name,
-                    mul=tmp, out_bf16=h, out_bf16_lo=hlo, ld_outb=ldh, opts=self.opts)
+        # precision="fp8", long-K level: LayerNorm -> e4m3 -> FFN-1 (activation -> e4m3 in its epilogue) -> FFN-2 (+ residual)
+        # (never a gated FFN: it has no e4m3 gate record -- `_packers` packs `.w8` with fp8_ok = not gated)
+        fp8 = (name + ".fc1.w8") in P and (name + ".fc2.w8") in P and ld == C and ldh == Hd and not ff.gated
+        k8 = self.FP8_ACT_LOG2 if fp8 else 0
+        rows = B * S
+        a = self._ln(P, name, x, rows, C, dev, fp8=fp8)
+        if fp8:
+            h = Act(self._buf("ffn.h8", (rows, Hd), torch.float8_e4m3fn, dev), None, Hd, float(2 ** k8))
         else:
-            L.igemm(a, w1, A_lo=alo, W_lo=w1lo, M=B * S, N=Hd, Cin=ld, bias=P[name + ".fc1.b"], act=ff.activation_name,
-                    out_bf16=h, out_bf16_lo=hlo, ld_outb=ldh, opts=self.opts)
-        w2, w2lo = P[name + ".fc2.w"]
-        L.igemm(h, w2, A_lo=hlo, W_lo=w2lo, M=B * S, N=C, Cin=ldh, bias=P[name + ".fc2.b"], residual=x, out_f32=x, opts=self.opts)
+            h = Act(*self._bf("ffn.h", rows, ldh, dev), ldh)
+        hidden = dict(act=ff.activation_name, out_bf16=h.hi, out_bf16_lo=h.lo, ld_outb=h.ld, out_fp8_log2=k8)
+        if ff.gated:
+            tmp = self._buf("ffn.tmp", (rows, Hd), torch.float32, dev)
+            self._gemm(P, name + ".fc1", a, M=rows, N=Hd, out_f32=tmp)
+            self._gemm(P, name + ".gate", a, M=rows, N=Hd, mul=tmp, **hidden)
+        else:
+            self._gemm(P, name + ".fc1", a, M=rows, N=Hd, **hidden)
+        self._gemm(P, name + ".fc2", h, M=rows, N=C, residual=x, out_f32=x)
 
     def _stack(self, P, name, blk: StackCuboidSelfAttentionBlock, x, B, S, C, level, dev):
         """StackCuboidSelfAttentionBlock.forward, eval branch (cuboid_transformer.py:1147-1156 / 1176-1186)."""
@@ -1074,10 +990,7 @@ class CuboidTransformerUNet(nn.Module):
                     L.add_rowtable(cur, P[f"upos{i - 1}"], B, Tn * Hn * Wn, Cn)
         # ---- head: Linear on the target frames x[:, in_len:] ----
         So = self.out_len * H * W
-        ld0 = pad64(C0)
-        a, alo = self._bf("final.a", B * So, ld0, dev)
-        L.cast_rows(cur, a, alo, B, S0, self.in_len * H * W, So, C0, C0, ld0, opts=self.opts)
+        a = self._cast(cur, "final.a", So, C0, dev, samples=B, rows_in=S0, row_off=self.in_len * H * W)
         out = torch.empty((B, self.out_len, H, W, C_lat), dtype=torch.float32, device=dev)
-        wf, wflo = P["final.w"]
-        L.igemm(a, wf, A_lo=alo, W_lo=wflo, M=B * So, N=C_lat, Cin=ld0, bias=P["final.b"], out_f32=out, opts=self.opts)
+        self._gemm(P, "final", a, M=B * So, N=C_lat, out_f32=out)
         return out

@@ -391,3 +391,64 @@ def test_modules_deepcopy_and_pickle():
         buf.seek(0)
         m3 = torch.load(buf, weights_only=False)
         assert m3.opts._state() == m.opts._state() and list(m3.state_dict()) == list(m.state_dict())
+
+
+def test_gemm_refuses_folded_weights_that_lost_their_tag(monkeypatch):
+    """HipEngine._gemm: a folded (hi + lo) weight is known to `_lib.igemm` by its `_pd_fold` attribute alone, which any .clone() / .to() /
+    view drops -- the launch would then silently run one product on the hi half.  The helper every weight launch goes through recognises
+    the folded shape (3-D, leading dimension 2 * taps) and raises, naming the layer, before any library call; tagged weights pass and
+    reach `igemm` with the layer's own tap count."""
+    from prediff_amd import _lib as L
+    from prediff_amd.engine import Act, HipEngine
+    from prediff_amd.packing import pack_conv, pack_linear
+    calls = []
+    monkeypatch.setattr(L, "igemm", lambda *a, **k: calls.append((a, k)))
+    monkeypatch.setattr(L, "lib", lambda: pytest.fail("the check needs no library"))
+    eng = HipEngine()
+    eng._init_engine("fp16x2", ("fp16x2",))
+    lin = pack_linear(torch.randn(24, 100), False, dtype=torch.float16, fold=True)
+    conv = pack_conv(torch.randn(16, 8, 3, 3, 3), False, dtype=torch.float16, fold=True)
+    assert lin[0].shape == (2, 24, 128) and conv[0].shape == (54, 16, 64) and lin[0]._pd_fold and conv[0]._pd_fold
+    a_lin = Act(torch.zeros(4, 128, dtype=torch.float16), None, 128)
+    a_conv = Act(torch.zeros(4, 64, dtype=torch.float16), None, 64)
+    geom = L.conv_geom(1, (1, 2, 2), (3, 3, 3))
+    out = torch.zeros(4, 24)
+    for name, (w, wlo), act, taps, g in (("blk.fc1", lin, a_lin, 1, None), ("blk.conv1", conv, a_conv, 27, geom)):
+        N = w.shape[1]
+        with pytest.raises(L.PrediffHipError, match=re.escape(name)):
+            eng._gemm({name + ".w": (w.clone(), wlo), name + ".b": None}, name, act, M=4, N=N, taps=taps, geom=g, out_f32=out)
+        assert not calls
+        eng._gemm({name + ".w": (w, wlo), name + ".b": None}, name, act, M=4, N=N, taps=taps, geom=g, out_f32=out)
+        (args, kw), = calls
+        assert args[1] is w and kw["taps"] == taps and kw["Cin"] == act.ld and kw["opts"] is eng.opts and not kw["fp8"]
+        calls.clear()
+    # unfolded records of the same layers are not mistaken for folded ones
+    for name, rec, act, taps, g in (("blk.fc1", pack_linear(torch.randn(24, 100), False), a_lin, 1, None),
+                                    ("blk.conv1", pack_conv(torch.randn(16, 8, 3, 3, 3), False), a_conv, 27, geom)):
+        eng._gemm({name + ".w": tuple(t.clone() if t is not None else None for t in rec)}, name, act, M=4, N=rec[0].shape[-2], taps=taps, geom=g,
+                  out_f32=out)
+        assert calls.pop()[1]["taps"] == taps
+
+
+def test_opts_for_caches_the_small_grid_copy():
+    """CuboidTransformerUNet._opts_for: the `small_grid` copy of the module's options is built once, not per launch, and rebuilt when a
+    caller changes any member of `net.opts` (an A/B preset, the profiling pointer); `net.opts` itself is never the small-grid object."""
+    from prediff_amd.cuboid_transformer_unet import CuboidTransformerUNet
+    from _cases import TINY_UNET_CFGS
+    net = CuboidTransformerUNet(**TINY_UNET_CFGS["axial"], precision="bf16")
+    assert net._opts_for(net.SPLITK_MAX_BATCH + 1) is net.opts and net.opts.small_grid == 0
+    o1 = net._opts_for(2)
+    assert o1 is not net.opts and o1.small_grid == 1 and net._opts_for(2) is o1 and net._opts_for(4) is o1
+    st = net.opts._state()
+    assert {k: v for k, v in o1._state().items() if k != "small_grid"} == {k: v for k, v in st.items() if k != "small_grid"}
+    net.opts.igemm_tile = 3
+    o2 = net._opts_for(2)
+    assert o2 is not o1 and o2.igemm_tile == 3 and o2.small_grid == 1 and net._opts_for(2) is o2
+    net.opts.trace = 4096
+    o3 = net._opts_for(2)
+    assert o3 is not o2 and o3.trace == 4096 and o3.igemm_tile == 3 and net._opts_for(2) is o3
+    net.opts.groupnorm_two_launches = 1
+    o4 = net._opts_for(2)
+    assert o4 is not o3 and o4.groupnorm_two_launches == 1 and net.opts.small_grid == 0
+    net.split_k = False
+    assert net._opts_for(2) is net.opts
