@@ -398,6 +398,42 @@ int pd_frame_score_update(const float* pred, const float* target, int M, const i
                           const int64_t* target_strides, float data_range, float* range_buf, int keep_seq, double* sums,
                           long long* counts, double* ws, int64_t ws_doubles, pd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Fréchet video distance (evaluation/fvd/): the pieces of the I3D feature engine that are not pd_igemm, and the feature moments.
+ * ------------------------------------------------------------------------------------------------- */
+/* I3DWrapper.preprocess (evaluation/fvd/torchmetrics_wrap.py:33-65) with the frame handling of FrechetVideoDistance.update (:223-233) in
+ * one launch.  x: fp32 frames read in place; sizes: host int64[5] = N, T, H, W, C (C = 1 is read as three equal channels, else C = 3);
+ * strides: host int64[5], element strides of those axes.  normalize != 0: x / 255 first; auto_t != 0: every frame twice
+ * (repeat_interleave along T: T2 = 2 T frames, else T2 = T).  Bilinear resize (align_corners = False, no antialias) of the short side to 224
+ * and the other side to ceil(side * 224 / short side), centre crop to 224 x 224 at offsets (size - 224) / 2, then 2 x - 1
+ * (rescale != 0; rescale == 0 leaves the value as it is: frames that are in [-1, 1] already, InceptionI3d.forward).
+ * out (/ out_lo: the low halves of the hi/lo engine, else NULL): the stem convolution's A operand, (N, T2, 224, 112, 64) 16-bit rows: the
+ * im2col along W at the stem's stride -- column 3 dw + c of row (n, t, y, ow) = frame[y][2 ow - 2 + dw][c] for dw = 0..6, zero outside the
+ * frame and in columns 21..63 (the stem then is a KT = 7, KH = 7, KW = 1 launch, strides (2, 2, 1), front pads (pt, 2, 0)).
+ * out_f32: NULL, or (N, T2, 224, 224, 3) fp32, the preprocessed frames before the operand rounding. */
+int pd_i3d_preprocess(const float* x, const int64_t* sizes, const int64_t* strides, int normalize, int auto_t, int rescale, pd_bf16* out,
+                      pd_bf16* out_lo, float* out_f32, const pd_call_opts* opts, pd_stream_t stream);
+
+/* MaxPool3dSamePadding (evaluation/fvd/pytorch_i3d.py:8-35) on channels-last fp32 x (B, T, H, W, C) rows of ld_in floats.  Per dimension
+ * pad = max(k - s, 0) if size % s == 0 else max(k - size % s, 0), front pad = pad / 2, output size (size + pad - k) / s + 1 (= ceil(size / s)).
+ * The padding holds the VALUE 0 and takes part in the max (the reference pads with zeros, then pools).  k >= s per dimension; C, ld_in,
+ * ld_out, ld_outb multiples of 4.  Writes fp32 rows (out_f32, ld_out) and / or 16-bit operand rows (outb[, outb_lo], ld_outb; columns
+ * >= C are not written). */
+int pd_maxpool3d_same(const float* x, float* out_f32, pd_bf16* outb, pd_bf16* outb_lo, int B, int T, int H, int W, int C, int ld_in,
+                      int kt, int kh, int kw, int st, int sh, int sw, int ld_out, int ld_outb, const pd_call_opts* opts, pd_stream_t stream);
+
+/* The end of InceptionI3d.forward (pytorch_i3d.py:301-306): AvgPool3d((2, 7, 7), stride 1) -> logits 1x1x1 convolution + bias -> mean over
+ * the T - 1 remaining time positions.  x (B, T, HW, C) fp32 channels last with the whole HW map inside the pool window (HW = 49), T >= 2;
+ * W (N, C) fp32 row major, bias (N) or NULL; pooled: (B, C) floats of workspace; out (B, N) fp32.  The pool commutes with the linear
+ * layer, so the frames are averaged first (weights (t >= 1) + (t <= T - 2) over 2 HW (T - 1)). */
+int pd_i3d_head(const float* x, const float* W, const float* bias, float* pooled, float* out, int B, int T, int HW, int C, int N,
+                pd_stream_t stream);
+
+/* FrechetVideoDistance.update's state (torchmetrics_wrap.py:241-247): f (n, d) fp32 rows of ld floats; sum[j] += sum_k f[k][j] and
+ * cov_sum[i][j] += sum_k f[k][i] f[k][j] in fp64, k ascending per entry (no atomics: the same inputs give the same bits).
+ * n >= 1, d <= 4096. */
+int pd_feature_moments_update(const float* f, int64_t n, int d, int ld, double* sum, double* cov_sum, pd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

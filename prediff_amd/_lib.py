@@ -159,6 +159,10 @@ _PROTOS = {
     "pd_frame_score_ws_doubles": (C.c_int64, [C.c_int, C.c_void_p]),
     "pd_frame_score_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_int]
                               + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "pd_i3d_preprocess": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(CallOpts), C.c_void_p]),
+    "pd_maxpool3d_same": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.POINTER(CallOpts), C.c_void_p]),
+    "pd_i3d_head": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
+    "pd_feature_moments_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -493,6 +497,49 @@ def frame_score_update(pred, target, M, sizes, pred_strides, target_strides, dat
     _check(lib().pd_frame_score_update(ptr(pred), ptr(target), int(M), _i64(sizes), _i64(pred_strides), _i64(target_strides),
                                        float(data_range), ptr(range_buf), 1 if keep_seq else 0, ptr(sums), ptr(counts), ptr(ws),
                                        ws.numel(), stream_ptr()), "pd_frame_score_update")
+
+
+I3D_RES, I3D_STEM_WO, I3D_STEM_LD = 224, 112, 64          # pd_i3d_preprocess: crop side, operand rows per image row, operand row length
+
+
+def i3d_preprocess(x, sizes, strides, normalize, auto_t, out, out_lo, out_f32=None, rescale=True, opts=None):
+    """sizes / strides: the (N, T, H, W, C) sizes and element strides of fp32 x (read in place); out[/out_lo]: (N, T2, 224, 112, 64) 16-bit
+    operand rows (the stem's im2col along W); out_f32: None or (N, T2, 224, 224, 3) fp32, the frames before the operand rounding.
+    rescale: [0, 1] -> [-1, 1] at the end (False: the frames are in [-1, 1] already)."""
+    _check(lib().pd_i3d_preprocess(ptr(x), _i64(sizes), _i64(strides), 1 if normalize else 0, 1 if auto_t else 0, 1 if rescale else 0, ptr(out), ptr(out_lo),
+                                   ptr(out_f32), _opts_ref(opts), stream_ptr()), "pd_i3d_preprocess")
+
+
+def same_pad(k, s, size):
+    """total SAME padding of one dimension (pytorch_i3d.py compute_pad); the front pad is half of it, rounded down"""
+    return max(k - s, 0) if size % s == 0 else max(k - size % s, 0)
+
+
+def same_out(k, s, size):
+    return (size + same_pad(k, s, size) - k) // s + 1
+
+
+def maxpool3d_same(x, B, thw, Cn, kernel, stride, out_f32=None, outb=None, outb_lo=None, ld_in=None, ld_out=None, ld_outb=None, opts=None):
+    """MaxPool3dSamePadding of channels-last fp32 x (B, *thw, Cn): zero padding that takes part in the max.  Returns the output (T, H, W)."""
+    T, H, W = thw
+    _check(lib().pd_maxpool3d_same(ptr(x), ptr(out_f32), ptr(outb), ptr(outb_lo), B, T, H, W, Cn, ld_in if ld_in is not None else Cn,
+                                   *kernel, *stride, ld_out if ld_out is not None else Cn, ld_outb if ld_outb is not None else pad64(Cn),
+                                   _opts_ref(opts), stream_ptr()), "pd_maxpool3d_same")
+    return tuple(same_out(k, s, n) for k, s, n in zip(kernel, stride, thw))
+
+
+def i3d_head(x, W, bias, pooled, out, B, T, HW, Cn, N):
+    """(2, 7, 7) average pool -> logits layer -> mean over time of fp32 channels-last x (B, T, HW, Cn) -> out (B, N) fp32."""
+    _check(lib().pd_i3d_head(ptr(x), ptr(W), ptr(bias), ptr(pooled), ptr(out), B, T, HW, Cn, N, stream_ptr()), "pd_i3d_head")
+
+
+def feature_moments_update(f, sum_, cov_sum):
+    """sum_ (d) += f.sum(0), cov_sum (d, d) += f^T f in fp64 for fp32 features f (n, d); fixed order, bit-reproducible."""
+    n, d = f.shape
+    _dev(f, torch.float32), _dev(sum_, torch.float64), _dev(cov_sum, torch.float64)
+    if sum_.numel() != d or tuple(cov_sum.shape) != (d, d):
+        raise PrediffHipError(f"feature_moments_update: state of {sum_.numel()} / {tuple(cov_sum.shape)} for {d} features")
+    _check(lib().pd_feature_moments_update(ptr(f), n, d, d, ptr(sum_), ptr(cov_sum), stream_ptr()), "pd_feature_moments_update")
 
 
 def attn_block_fused_supported(Cn, heads, vol):

@@ -39,6 +39,34 @@ def seeded_state_dict(template: Mapping[str, torch.Tensor], seed: int) -> Dict[s
     return out
 
 
+def seeded_i3d_state_dict(template: Mapping[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded weights for InceptionI3d (conv + BatchNorm + ReLU, 57 layers deep): conv weights randn * sqrt(2 / fan_in) so that the ReLU
+    stack keeps O(1) activations, BatchNorm weight 1 + 0.1 r, bias 0.1 r, running_mean 0.1 r, running_var (1 + 0.1 r)^2 (positive, which
+    `seeded_state_dict`'s zero-centred draw is not); conv biases 0.1 r; integer buffers kept."""
+    out = {}
+    for k in template:
+        v = template[k]
+        if not torch.is_floating_point(v):
+            out[k] = v.detach().clone().cpu()
+            continue
+        g = torch.Generator(device="cpu")
+        g.manual_seed((seed * 1000003 + zlib.crc32(("i3d:" + k).encode())) % (2 ** 63 - 1))
+        shape = tuple(v.shape)
+        r = torch.randn(shape, generator=g, dtype=torch.float32)
+        if len(shape) >= 2:
+            fan_in = 1
+            for s_ in shape[1:]:
+                fan_in *= s_
+            out[k] = r * math.sqrt(2.0 / fan_in)
+        elif k.endswith("bn.weight"):
+            out[k] = 1.0 + 0.1 * r
+        elif k.endswith("running_var"):
+            out[k] = (1.0 + 0.1 * r) ** 2
+        else:                                   # bn.bias, running_mean, conv bias
+            out[k] = 0.1 * r
+    return out
+
+
 def heavy_tailed_state_dict(template: Mapping[str, torch.Tensor], seed: int, nu: float = 3.0, outlier: float = 30.0,
                             n_outlier: int = 2) -> Dict[str, torch.Tensor]:
     """Checkpoint-like stress weights (no trained checkpoint exists offline): every matrix / filter is Student-t(nu) distributed with
