@@ -97,7 +97,9 @@ typedef struct pd_igemm_args {
   int32_t vec_epilogue;    /* set by the library */
   uint32_t a_bytes, w_bytes; /* set by the library: extent of one A / W batch (buffer-descriptor bounds) */
   int32_t debug_flags;     /* profiling ablations only: 1 skip main loop, 2 skip stores, 4 skip activation, 8 keep the dense tap loop of the 256 x 256 Conv3d kernels (tile 11 skips nothing: no effect),
-                              16 the automatic choice keeps the tap-streamed 256 x 256 kernel where it would take a halo-staged one (tile 10 or 11), 64 four-phase K-tile (0 in production) */
+                              16 the automatic choice keeps the tap-streamed 256 x 256 kernel where it would take a halo-staged one (tile 10 or 11), 64 four-phase K-tile (0 in production),
+                              128 (tests of pd_igemm_mx, which alone reads it; pd_igemm ignores it) K-split into two to four slices whenever a workspace is given, whatever the
+                              grid: the split form at shapes too short (fewer than 32 K-tiles) to split by themselves */
   int32_t ksplit;          /* set by the library: K-slices of a split-K launch (1 = none) */
   float* splitk_ws;        /* caller workspace for split-K partial sums (fp32, splitk_ws_elems elements) or NULL: without it a launch
                               is never split.  Used for small grids (few trajectories per launch): the K loop of a long-K launch is cut
@@ -121,6 +123,45 @@ typedef struct pd_igemm_args {
   int32_t reserved0;
 } pd_igemm_args;
 int pd_igemm(const pd_igemm_args* a, pd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * MX (OCP microscaling) e4m3 operands: every 32 consecutive K elements of a row share one E8M0 scale byte (DESIGN.md section 7
+ * states the format).  An MX operand is two byte arrays: the payload, rows of `ld` bytes, and the scales, rows of `ld / 32`
+ * bytes; columns [K, ld) are padding (zero payload, scale byte 0).  pd_igemm_mx reads operands with ld % 128 == 0, so that a
+ * 128-element K-tile never leaves a row (for a convolution: never spans two filter taps).
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct pd_mx_operands {
+  const uint8_t* a_scales;    /* [input rows][ld_a_scales] E8M0 bytes of A (input rows: B * Ti * Hi * Wi, as the rows of A) */
+  const uint8_t* w_scales;    /* [tap][N][ld_w_scales] E8M0 bytes of W */
+  int64_t w_scale_tap_stride; /* bytes between the taps of w_scales */
+  int32_t ld_a_scales, ld_w_scales;   /* = lda / 32, ldw / 32 (multiples of 4) */
+  int32_t reserved0, reserved1;
+} pd_mx_operands;
+int pd_sizeof_mx_operands(void);
+
+/* pd_igemm on MX operands: A and W hold e4m3 payload bytes (lda / ldw / strides count bytes; Cin = the padded K per tap, Cin % 128 == 0,
+ * lda, ldw % 128 == 0), `mx` their block scales; the scaled MFMA applies both scale bytes of every 32-element block.  Everything else
+ * (geometry, epilogue, alpha, split-K through `splitk_ws`) as pd_igemm with fp8 != 0; `fp8`, `split`, `w_fold`, `operand`, `tile` and
+ * `out_fp8_log2` of `a` must be 0 (the library sets what it needs).  Row-wise linear layers and stride-1, un-upsampled convolutions. */
+int pd_igemm_mx(const pd_igemm_args* a, const pd_mx_operands* mx, pd_stream_t stream);
+
+/* fp32 rows -> MX e4m3: q (rows, ld) payload bytes, scales (rows, ld / 32); x rows of ld_x floats; K % 32 == 0, ld % 32 == 0, ld >= K.
+ * Per block: scale byte = clamp(127 + e, 0, 254) with e = floor(log2(amax)) - 8, one more where amax * 2^-e would exceed 448 (so that
+ * no payload saturates); payload = e4m3(x * 2^-e), round to nearest even.  An all-zero block: scale byte 0, zero payload.  Non-finite
+ * input is the caller's error. */
+int pd_quantize_mx(const float* x, uint8_t* q, uint8_t* scales, int64_t rows, int K, int ld_x, int ld, pd_stream_t stream);
+
+/* pd_layernorm with an MX output (the A operand of a pd_igemm_mx linear): out (rows, ld_out) payload, scales (rows, ld_out / 32);
+ * C % 32 == 0, ld_out % 32 == 0, C <= ld_out <= the last 256-column block of C. */
+int pd_layernorm_mx(const float* x, const float* gamma, const float* beta, uint8_t* out, uint8_t* scales, int64_t rows, int C, int ld_out,
+                    float eps, pd_stream_t stream);
+
+/* pd_groupnorm_silu with an MX output (the A operand of a pd_igemm_mx convolution): out (B * S, ld_out) payload, scales
+ * (B * S, ld_out / 32).  C % 32 == 0, C/4 divides 256, 4 | C/G, ld_out % 32 == 0, ld_out >= C, ld_out - C < 128 (pad columns are
+ * written: zero payload, scale byte 0). */
+int pd_groupnorm_silu_mx(const float* x, const float* gamma, const float* beta, const float* ss_scale, const float* ss_shift, int ld_ss,
+                         double* partials, uint8_t* out, uint8_t* scales, int B, int S, int C, int G, int ld_out, float eps, int silu,
+                         pd_stream_t stream);
 
 /* nn.LayerNorm(eps, affine) over the last dim C of fp32 rows -> bf16 (hi[, lo]) rows of ld_out elements
  * (pad columns [C, ld_out) are written as zero).  cuboid_transformer.py:813 (attn pre-norm), :197 (FFN pre-norm). */

@@ -49,6 +49,12 @@ class CuboidAttnArgs(C.Structure):
                 ("operand", C.c_int32), ("qkv_fp8_log2", C.c_int32)]
 
 
+class MxOperands(C.Structure):
+    """pd_mx_operands: the E8M0 block scales of the two operands of a pd_igemm_mx launch"""
+    _fields_ = [("a_scales", C.c_void_p), ("w_scales", C.c_void_p), ("w_scale_tap_stride", C.c_int64), ("ld_a_scales", C.c_int32),
+                ("ld_w_scales", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+
+
 OPERAND = {"bf16": 0, "fp16": 1}            # enum pd_operand
 
 
@@ -110,6 +116,11 @@ _PROTOS = {
     "pd_sizeof_cuboid_attn_args": (C.c_int, []),
     "pd_sizeof_call_opts": (C.c_int, []),
     "pd_igemm": (C.c_int, [C.POINTER(IgemmArgs), C.c_void_p]),
+    "pd_sizeof_mx_operands": (C.c_int, []),
+    "pd_igemm_mx": (C.c_int, [C.POINTER(IgemmArgs), C.POINTER(MxOperands), C.c_void_p]),
+    "pd_quantize_mx": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pd_layernorm_mx": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "pd_groupnorm_silu_mx": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p]),
     "pd_layernorm": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int, C.c_float, C.POINTER(CallOpts), C.c_void_p]),
     "pd_layernorm_fp8": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "pd_patch_merge_layernorm": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 9 + [C.c_float, C.c_void_p]),
@@ -181,7 +192,8 @@ def lib():
             f.restype = res
             f.argtypes = args
         if (l.pd_sizeof_igemm_args() != C.sizeof(IgemmArgs) or l.pd_sizeof_cuboid_attn_args() != C.sizeof(CuboidAttnArgs)
-                or l.pd_sizeof_call_opts() != C.sizeof(CallOpts) or l.pd_abi_version() != ABI_VERSION):
+                or l.pd_sizeof_call_opts() != C.sizeof(CallOpts) or l.pd_sizeof_mx_operands() != C.sizeof(MxOperands)
+                or l.pd_abi_version() != ABI_VERSION):
             raise PrediffHipError(f"{LIB_PATH} is stale: its ABI version / argument structs do not match prediff_amd/_lib.py "
                                   f"(rebuild with `make -C prediff_amd/csrc`)")
         _lib = l
@@ -231,6 +243,14 @@ def igemm(A, W, *, M, N, Cin, lda=None, ldw=None, taps=1, w_tap_stride=0, geom=N
           outb_batch_stride=0, res_batch_stride=0, tile=0, debug_flags=0, splitk_ws=None, fp8=False, out_fp8_log2=0, opts=None):
     """Thin wrapper around pd_igemm.  `geom` = dict(B,Ti,Hi,Wi,To,Ho,Wo,KT,KH,KW,st,sh,sw,pt,ph,pw,ut,uh,uw) or None
     for a plain linear layer.  `opts` (CallOpts): the operand type of A / W / out_bf16 and the caller's A/B presets for this launch."""
+    a = _igemm_args(**{k: v for k, v in locals().items()})
+    _check(lib().pd_igemm(C.byref(a), stream_ptr()), "pd_igemm")
+
+
+def _igemm_args(A, W, *, M, N, Cin, lda, ldw, taps, w_tap_stride, geom, A_lo, W_lo, bias, rowvec, rows_per_sample, residual, res_period,
+                ld_res, mul, act, alpha, out_f32, out_bf16, out_bf16_lo, ld_out, ld_outb, nbatch, a_batch_stride, w_batch_stride,
+                out_batch_stride, outb_batch_stride, res_batch_stride, tile, debug_flags, splitk_ws, fp8, out_fp8_log2, opts):
+    """pd_igemm_args of a launch (the keywords of `igemm`)"""
     a = IgemmArgs()
     if opts is not None:
         a.operand = 0 if fp8 else opts.operand          # (e4m3 operands: the 16-bit OUTPUT of such a launch is bfloat16)
@@ -276,7 +296,83 @@ def igemm(A, W, *, M, N, Cin, lda=None, ldw=None, taps=1, w_tap_stride=0, geom=N
     a.out_fp8_log2 = out_fp8_log2     # k > 0: out_bf16 is an e4m3 byte tensor receiving e4m3(v * 2^k)
     if splitk_ws is not None:       # fp32 workspace: lets the library split the K loop of small-grid, long-K launches
         a.splitk_ws, a.splitk_ws_elems = ptr(splitk_ws), splitk_ws.numel()
-    _check(lib().pd_igemm(C.byref(a), stream_ptr()), "pd_igemm")
+    return a
+
+
+def _mx_pair(t, s, what):
+    """payload / scale arrays of an MX operand: (rows..., ld) e4m3 bytes and (rows..., ld / 32) uint8, on the GPU, contiguous"""
+    if t.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise PrediffHipError(f"{what}: the MX payload must be float8_e4m3fn (or raw uint8) bytes, got {t.dtype}")
+    _dev(t)
+    _dev(s, torch.uint8)
+    if s.device != t.device:
+        raise PrediffHipError(f"{what}: payload and scales live on different devices")
+    ld = t.shape[-1]
+    if ld % 32 or tuple(s.shape) != tuple(t.shape[:-1]) + (ld // 32,):
+        raise PrediffHipError(f"{what}: scales {tuple(s.shape)} do not match one byte per 32 elements of payload {tuple(t.shape)}")
+    return ld
+
+
+def igemm_mx(A, a_scales, W, w_scales, *, M, N, taps=1, geom=None, bias=None, rowvec=None, rows_per_sample=0, residual=None, res_period=0,
+             ld_res=None, mul=None, act="none", alpha=1.0, out_f32=None, out_bf16=None, ld_out=None, ld_outb=None, debug_flags=0,
+             splitk_ws=None, opts=None):
+    """pd_igemm_mx: the implicit GEMM on MX operands -- e4m3 payloads A (input rows, ld) and W ((taps,) N, ld) with their E8M0 block
+    scales (packing.quantize_mx / pack_linear_mx / pack_conv_mx, or the *_mx producers); ld % 128 == 0.  A 16-bit output is bfloat16."""
+    lda, ldw = _mx_pair(A, a_scales, "pd_igemm_mx A"), _mx_pair(W, w_scales, "pd_igemm_mx W")
+    if lda != ldw or lda % 128:
+        raise PrediffHipError(f"pd_igemm_mx: A rows of {lda} and W rows of {ldw} bytes: both operands need the same row length, a multiple of 128")
+    if W.numel() != taps * N * ldw:
+        raise PrediffHipError(f"pd_igemm_mx: W {tuple(W.shape)} is not ({taps}, {N}, {ldw})")
+    rows_in = M if geom is None else geom["B"] * geom["Ti"] * geom["Hi"] * geom["Wi"]
+    if A.numel() != rows_in * lda:
+        raise PrediffHipError(f"pd_igemm_mx: A {tuple(A.shape)} is not ({rows_in}, {lda})")
+    presets = dict(debug_flags=debug_flags | (opts.igemm_debug_or if opts is not None else 0))
+    a = _igemm_args(A, W, M=M, N=N, Cin=lda, lda=lda, ldw=ldw, taps=taps, w_tap_stride=N * ldw if taps > 1 else 0, geom=geom, A_lo=None,
+                    W_lo=None, bias=bias, rowvec=rowvec, rows_per_sample=rows_per_sample, residual=residual, res_period=res_period,
+                    ld_res=ld_res, mul=mul, act=act, alpha=alpha, out_f32=out_f32, out_bf16=out_bf16, out_bf16_lo=None, ld_out=ld_out,
+                    ld_outb=ld_outb, nbatch=1, a_batch_stride=0, w_batch_stride=0, out_batch_stride=0, outb_batch_stride=0,
+                    res_batch_stride=0, tile=0, splitk_ws=splitk_ws, fp8=False, out_fp8_log2=0, opts=None, **presets)
+    if opts is not None:
+        a.disable_256, a.splitk_max_tiles = 0, opts.igemm_splitk_max_tiles
+    m = MxOperands()
+    m.a_scales, m.w_scales = ptr(a_scales), ptr(w_scales)
+    m.ld_a_scales, m.ld_w_scales = lda // 32, ldw // 32
+    m.w_scale_tap_stride = N * (ldw // 32) if taps > 1 else 0
+    _check(lib().pd_igemm_mx(C.byref(a), C.byref(m), stream_ptr()), "pd_igemm_mx")
+
+
+def quantize_mx(x, q, scales, rows, K, ld=None, ld_x=None):
+    """fp32 rows -> MX e4m3 (pd_quantize_mx): q (rows, ld) payload, scales (rows, ld / 32); columns [K, ld) are padding."""
+    _dev(x, torch.float32)
+    ld = _mx_pair(q, scales, "pd_quantize_mx") if ld is None else ld
+    ld_x = K if ld_x is None else ld_x
+    if K % 32:
+        raise PrediffHipError(f"pd_quantize_mx: K = {K} is not a multiple of 32 (one scale per 32 elements)")
+    if x.numel() < rows * ld_x or q.numel() != rows * ld or scales.numel() != rows * (ld // 32):
+        raise PrediffHipError(f"pd_quantize_mx: x {tuple(x.shape)} / q {tuple(q.shape)} / scales {tuple(scales.shape)} do not hold {rows} rows of {K} (ld {ld})")
+    _check(lib().pd_quantize_mx(ptr(x), ptr(q), ptr(scales), rows, K, ld_x, ld, stream_ptr()), "pd_quantize_mx")
+
+
+def layernorm_mx(x, gamma, beta, out, scales, rows, Cn, eps=1e-5):
+    """LayerNorm -> MX e4m3 rows (pd_layernorm_mx): the A operand of a pd_igemm_mx linear."""
+    ld = _mx_pair(out, scales, "pd_layernorm_mx")
+    for t in (x, gamma, beta):
+        _dev(t, torch.float32)
+    if out.numel() != rows * ld or x.numel() != rows * Cn:
+        raise PrediffHipError(f"pd_layernorm_mx: x {tuple(x.shape)} / out {tuple(out.shape)} do not hold {rows} rows of {Cn}")
+    _check(lib().pd_layernorm_mx(ptr(x), ptr(gamma), ptr(beta), ptr(out), ptr(scales), rows, Cn, ld, eps, stream_ptr()), "pd_layernorm_mx")
+
+
+def groupnorm_silu_mx(x, gamma, beta, partials, out, scales, B, S, Cn, G, eps, silu=True, ss_scale=None, ss_shift=None, ld_ss=0):
+    """GroupNorm [-> scale-shift] [-> SiLU] -> MX e4m3 rows (pd_groupnorm_silu_mx): the A operand of a pd_igemm_mx convolution."""
+    ld = _mx_pair(out, scales, "pd_groupnorm_silu_mx")
+    for t in (x, gamma, beta):
+        _dev(t, torch.float32)
+    _dev(partials, torch.float64)
+    if out.numel() != B * S * ld or x.numel() != B * S * Cn or partials.numel() < B * groupnorm_nchunk(S, Cn) * G * 2:
+        raise PrediffHipError(f"pd_groupnorm_silu_mx: x {tuple(x.shape)} / out {tuple(out.shape)} / partials do not hold {B} x {S} rows of {Cn}")
+    _check(lib().pd_groupnorm_silu_mx(ptr(x), ptr(gamma), ptr(beta), ptr(ss_scale), ptr(ss_shift), ld_ss, ptr(partials), ptr(out),
+                                      ptr(scales), B, S, Cn, G, ld, eps, 1 if silu else 0, stream_ptr()), "pd_groupnorm_silu_mx")
 
 
 def conv_geom(B, in_thw, kernel, stride=(1, 1, 1), pad=(1, 1, 1), up=(1, 1, 1), out_thw=None, virt_thw=None):

@@ -14,6 +14,7 @@ extern "C" int pd_abi_version(void) { return 4; }   // 2: per-call options (pd_c
 extern "C" int pd_sizeof_igemm_args(void) { return (int)sizeof(pd_igemm_args); }
 extern "C" int pd_sizeof_cuboid_attn_args(void) { return (int)sizeof(pd_cuboid_attn_args); }
 extern "C" int pd_sizeof_call_opts(void) { return (int)sizeof(pd_call_opts); }
+extern "C" int pd_sizeof_mx_operands(void) { return (int)sizeof(pd_mx_operands); }
 
 static inline unsigned grid_for(int64_t n) { return (unsigned)min((int64_t)8192, (n + 255) / 256); }
 

@@ -287,6 +287,30 @@ int pd_igemm256_launch_splitk(const pd_igemm_args& a, int kind, hipStream_t s);
 bool pd_conv3d_halo_supported(const pd_igemm_args& a, int kind, int level);
 int pd_conv3d_halo_launch(const pd_igemm_args& a, int level, hipStream_t s);
 
+// The two derived fields of a validated launch, shared by pd_igemm and pd_igemm_mx (mx.hip).
+// a_bytes / w_bytes: the extents of the operands' buffer descriptors (a.fp8: one byte per element); false = one does not fit a descriptor
+bool pd_igemm_operand_extents(pd_igemm_args& a) {
+  const int eb = a.fp8 ? 1 : 2;
+  const int64_t abytes = (int64_t)a.B * a.Ti * a.Hi * a.Wi * (int64_t)a.lda * eb;
+  const int64_t wbytes = ((int64_t)(a.taps - 1) * a.w_tap_stride + (int64_t)a.N * a.ldw) * eb;
+  if (abytes >= 0xfffffe00ll || wbytes >= 0xfffffe00ll) return false;
+  a.a_bytes = (uint32_t)abytes;
+  a.w_bytes = (uint32_t)wbytes;
+  return true;
+}
+// vec_epilogue: 0 = scalar stores, 1 = four columns per store, 2 = 16 B bf16 stores
+int pd_igemm_vec_epilogue(const pd_igemm_args& a) {
+  const bool v4 = ((a.N & 3) == 0) && (!a.out_f32 || (a.ld_out & 3) == 0) && (!a.out_bf16 || (a.ld_outb & 3) == 0) &&
+                  (!a.residual || (a.ld_res & 3) == 0) && (!a.rowvec || (a.ld_rowvec & 3) == 0) &&
+                  (!a.mul || (a.ld_mul & 3) == 0) && (((uintptr_t)a.out_f32 | (uintptr_t)a.residual | (uintptr_t)a.rowvec |
+                  (uintptr_t)a.mul) & 15) == 0 && (((uintptr_t)a.out_bf16 | (uintptr_t)a.out_bf16_lo) & 7) == 0 &&
+                  ((a.out_batch_stride | a.outb_batch_stride | a.res_batch_stride) & 3) == 0;
+  if (v4 && !a.out_f32 && a.out_bf16 && (a.N & 7) == 0 && (a.ld_outb & 7) == 0 && (a.outb_batch_stride & 7) == 0 &&
+      (((uintptr_t)a.out_bf16 | (uintptr_t)a.out_bf16_lo) & 15) == 0)
+    return 2;
+  return v4 ? 1 : 0;
+}
+
 #if !PD_IS_F16
 extern "C" int pd_f16_igemm(const pd_igemm_args*, pd_stream_t);
 #endif
@@ -314,26 +338,12 @@ extern "C" int PD_ENTRY(igemm)(const pd_igemm_args* pa, pd_stream_t stream) {
     PD_CHECK_ARG((a.Cin & 127) == 0 && (a.lda & 15) == 0 && (a.ldw & 15) == 0, "pd_igemm: fp8 operands need Cin %% 128 == 0 and lda/ldw %% 16 == 0");
     PD_CHECK_ARG(!a.split && a.nbatch <= 1, "pd_igemm: fp8 operands: no hi/lo split, no batch");
   }
-  {
-    const int eb = a.fp8 ? 1 : 2;
-    const int64_t abytes = (int64_t)a.B * a.Ti * a.Hi * a.Wi * (int64_t)a.lda * eb;
-    const int64_t wbytes = ((int64_t)(a.taps - 1) * a.w_tap_stride + (int64_t)a.N * a.ldw) * eb;
-    PD_CHECK_ARG(abytes < 0xfffffe00ll && wbytes < 0xfffffe00ll, "pd_igemm: operand larger than a 4 GiB buffer descriptor");
-    a.a_bytes = (uint32_t)abytes;
-    a.w_bytes = (uint32_t)wbytes;
-  }
+  PD_CHECK_ARG(pd_igemm_operand_extents(a), "pd_igemm: operand larger than a 4 GiB buffer descriptor");
   PD_CHECK_ARG(!a.split || (a.A_lo && a.W_lo), "pd_igemm: split needs A_lo and W_lo");
   PD_CHECK_ARG(!a.rowvec || a.rows_per_sample > 0, "pd_igemm: rowvec needs rows_per_sample");
   PD_CHECK_ARG(a.out_f32 || a.out_bf16, "pd_igemm: no output");
   hipStream_t s = (hipStream_t)stream;
-  a.vec_epilogue = ((a.N & 3) == 0) && (!a.out_f32 || (a.ld_out & 3) == 0) && (!a.out_bf16 || (a.ld_outb & 3) == 0) &&
-                   (!a.residual || (a.ld_res & 3) == 0) && (!a.rowvec || (a.ld_rowvec & 3) == 0) &&
-                   (!a.mul || (a.ld_mul & 3) == 0) && (((uintptr_t)a.out_f32 | (uintptr_t)a.residual | (uintptr_t)a.rowvec |
-                   (uintptr_t)a.mul) & 15) == 0 && (((uintptr_t)a.out_bf16 | (uintptr_t)a.out_bf16_lo) & 7) == 0 &&
-                   ((a.out_batch_stride | a.outb_batch_stride | a.res_batch_stride) & 3) == 0;
-  if (a.vec_epilogue && !a.out_f32 && a.out_bf16 && (a.N & 7) == 0 && (a.ld_outb & 7) == 0 && (a.outb_batch_stride & 7) == 0 &&
-      (((uintptr_t)a.out_bf16 | (uintptr_t)a.out_bf16_lo) & 15) == 0)
-    a.vec_epilogue = 2;   // 16 B bf16 stores
+  a.vec_epilogue = pd_igemm_vec_epilogue(a);
   if (a.out_fp8_log2 > 0) {
     PD_CHECK_ARG(a.vec_epilogue == 2 && !a.out_bf16_lo && !a.split && a.out_fp8_log2 <= 16,
                  "pd_igemm: an e4m3 output needs the 8-column vector epilogue (out_bf16 only, N %% 8 == 0, ld_outb %% 8 == 0, 16 B aligned), no split");

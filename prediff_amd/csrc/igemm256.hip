@@ -39,6 +39,8 @@ namespace PD_NS {
 
 #define BLDS16(rsrc, ldsptr, voff, soff) \
   __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (__attribute__((address_space(3))) void*)(ldsptr), 16, (voff), (soff), 0, 0)
+#define BLDS4(rsrc, ldsptr, voff, soff) \
+  __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (__attribute__((address_space(3))) void*)(ldsptr), 4, (voff), (soff), 0, 0)
 #define PD_OOB 0xffffff00u
 #define VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define PHASE_SYNC()                   \
@@ -73,12 +75,29 @@ __device__ __forceinline__ f32x4 mfma_f8(const Frag256<true>& a, const Frag256<t
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a.v, b.v, c, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);   // e4m3 x e4m3, block scales 2^0
 }
 __device__ __forceinline__ f32x4 mfma_f8(const Frag256<false>&, const Frag256<false>&, f32x4 c) { return c; }
+// MX: byte 0 of the scale registers of lane l16 + 16 kb holds the E8M0 scale of K-block kb of row / column l16
+__device__ __forceinline__ f32x4 mfma_mx(const Frag256<true>& a, const Frag256<true>& b, int sa, int sb, f32x4 c) {
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a.v, b.v, c, 0, 0, 0, sa, 0, sb);
+}
+[[maybe_unused]] __device__ __forceinline__ f32x4 mfma_mx(const Frag256<false>&, const Frag256<false>&, int, int, f32x4 c) { return c; }
 __device__ __forceinline__ f32x4 mfma_op16(const Frag256<false>& a, const Frag256<false>& b, int ks, f32x4 c) {
   return mfma_16x16x32(a.v[ks], b.v[ks], c);
 }
 __device__ __forceinline__ f32x4 mfma_op16(const Frag256<true>&, const Frag256<true>&, int, f32x4 c) { return c; }
 constexpr int HT = 128 * 128;   // bytes of one half tile: 128 rows x 64 bf16
 constexpr int KBUF = 4 * HT;    // one K-tile buffer: A half 0, A half 1, W half 0, W half 1
+constexpr int SBUF = 512 * 4;   // MX: the scale dwords of one K-tile, one per tile row (A rows 0-255, then W rows 0-255), behind the two K-tile buffers
+
+// MX: the block scales of the two operands as the kernel reads them (pd_igemm256_launch_mx fills it from pd_mx_operands)
+struct MxK {
+  const uint8_t* sa;          // [input rows][ldsa]
+  const uint8_t* sw;          // [tap][N][ldsw]
+  uint32_t sa_bytes, sw_bytes;
+  int32_t ldsa, ldsw;
+  uint32_t sw_tap;            // bytes between the taps of sw
+};
+template <class T>
+__device__ __forceinline__ const T& mx_operand(const T& t) { return t; }
 
 }
 
@@ -110,8 +129,21 @@ constexpr int KBUF = 4 * HT;    // one K-tile buffer: A half 0, A half 1, W half
 // WF (round 6): folded weights (pd_igemm_args.w_fold, precision="fp16x2") -- the weight slabs of W_lo walk the activation gather of the W_hi slabs.
 // A template flag, not a run-time test: the one-product instantiations -- the headline's Conv3d kernel -- keep the instruction stream they had
 // (the run-time form added 12 scalar instructions to every K-tile of the hot loop and cost the kernel 2-5 %).
-template <int KIND, int RT, bool SK = false, bool F8 = false, bool SP = false, bool P2 = true, bool WF = false>
-__global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
+// MX (a template flag like WF: every other instantiation keeps its instruction stream): e4m3 operands with one E8M0 scale byte per 32 K
+// elements (the OCP MX layout; pd_igemm_mx).  What differs from F8 is the scale stream alone:
+//   * the (lane, byte) -> k assignment stays.  The 16-byte slots lg and 4 + lg a lane reads are the instruction's own K order: registers
+//     0-3 of lane group lg are K [16 lg, 16 lg + 16) of the 128-element tile, registers 4-7 K [64 + 16 lg, 64 + 16 lg + 16).  The hardware
+//     does NOT scale a lane's 32 bytes by the lane's own scale byte: it takes the scale of K-block kb (K [32 kb, 32 kb + 32)) of row i from
+//     lane i + 16 kb (measured on the MI355X with one-hot payload blocks against one-hot scales).  So lane (l16, lg) supplies byte lg of
+//     row l16's scale dword and the fragments need no relayout;
+//   * the scale stream: one more DMA instruction per K-tile (4 B per lane) stages the scale dword -- the four block scales of the K-tile --
+//     of each of the 512 tile rows (thread t: A row t, or W row t - 256) into SBUF bytes behind the operand buffers, issued with the A
+//     halves of the same K-tile (so the counted vmcnt of the W stream covers it) and read, one byte per lane and 16 x 16 tile, with the
+//     fragments (same hazards as the A halves).  Rows outside the matrix / taps outside the image read scale byte 0 against a zero payload.
+template <int KIND, int RT, bool SK = false, bool F8 = false, bool SP = false, bool P2 = true, bool WF = false, bool MX = false, class... MXA>
+__global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p, const MXA... mxa) {
+  static_assert(sizeof...(MXA) == (MX ? 1 : 0), "MX: one MxK operand behind the arguments; nothing else");
+  static_assert(!MX || (F8 && P2 && !SP && !WF && RT == 8), "MX: the two-phase e4m3 form, 256-row tiles");
   static_assert(!WF || (!F8 && !SP), "folded weights: 16-bit operands, no hi/lo split");
   static_assert(!SP || (!SK && !F8), "the hi/lo form: bf16 operands, no K-slices");
   constexpr uint32_t EB = F8 ? 1u : 2u;           // bytes per operand element
@@ -189,6 +221,35 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
       const int n = n0 + hh * 128 + i * 64 + srow;
       woff[hh][i] = n < p.N ? ((uint32_t)n * (uint32_t)p.ldw) * EB + w_sel : PD_OOB;
     }
+  // MX: this thread's tile row of the scale stream (waves 0-3: A row tid, waves 4-7: W row tid - 256)
+  struct SRow { uint32_t off, coord, base; int rd_a, rd_b; };
+  [[maybe_unused]] SRow sr;
+  if constexpr (MX) {
+    const MxK& mx = mx_operand(mxa...);
+    uint32_t s_off = PD_OOB, s_coord = 0, s_base = 0;
+    if (wave < 4) {
+      const int m = m0 + tid;
+      const bool ok = m < p.M;
+      if (KIND == 0) {
+        s_off = ok ? (uint32_t)m * (uint32_t)mx.ldsa : PD_OOB;
+      } else {
+        const int hw_o = p.Ho * p.Wo, thw_o = p.To * hw_o;
+        const int mm = ok ? m : 0;
+        const int b = mm / thw_o, r1 = mm - b * thw_o;
+        const int ot = r1 / hw_o, r2 = r1 - ot * hw_o;
+        const int oh = r2 / p.Wo, ow = r2 - oh * p.Wo;
+        s_coord = (uint32_t)ot | ((uint32_t)oh << 10) | ((uint32_t)ow << 20) | (ok ? 0u : 0x80000000u);
+        s_base = (uint32_t)b * (uint32_t)(p.Ti * p.Hi * p.Wi);
+      }
+    } else {
+      const int n = n0 + tid - 256;
+      s_off = n < p.N ? (uint32_t)n * (uint32_t)mx.ldsw : PD_OOB;
+    }
+    sr.off = s_off; sr.coord = s_coord; sr.base = s_base;
+    // the lane's scale byte inside an SBUF: A tile i at rd_a + i * 64, W tile j at rd_b + j * 64
+    sr.rd_a = 2 * KBUF + (wr * 128 + (lane & 15)) * 4 + (lane >> 4);
+    sr.rd_b = 2 * KBUF + (256 + wc * 64 + (lane & 15)) * 4 + (lane >> 4);
+  }
   const int kchunks = p.Cin >> KSH;
   const int khw = p.KH * p.KW;
   // ---- whole-tile tap skipping (KIND 2, un-split launches): when the input frame of a temporal filter tap lies outside [0, Ti) for
@@ -256,6 +317,26 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
     BLDS16(rA, dst, aoff[hh][0], ka);
     BLDS16(rA, dst + 64 * 128, aoff[hh][1], ka);
   };
+  auto issue_s = [&](int buf) {            // MX: the scale dwords of the A stream's current K-tile (both operands); before next_a()
+    if constexpr (MX) {
+      const MxK& mx = mx_operand(mxa...);
+      const bool is_a = wave < 4;
+      const auto rS = __builtin_amdgcn_make_buffer_rsrc((void*)(is_a ? mx.sa : mx.sw), 0, is_a ? mx.sa_bytes : mx.sw_bytes, 0x00020000);
+      uint32_t off = sr.off;
+      int so = a_kc * 4;
+      if (is_a) {
+        if (KIND != 0) {                   // (un-upsampled, stride-1 launches only: the input row of the current tap)
+          const uint32_t c = sr.coord;
+          const int vt = (int)(c & 1023u) - p.pt + a_kt, vh = (int)((c >> 10) & 1023u) - p.ph + a_kh, vw = (int)((c >> 20) & 1023u) - p.pw + a_kw;
+          const bool ok = !(c >> 31) && (unsigned)vt < (unsigned)p.Ti && (unsigned)vh < (unsigned)p.Hi && (unsigned)vw < (unsigned)p.Wi;
+          off = ok ? (sr.base + (uint32_t)((vt * p.Hi + vh) * p.Wi + vw)) * (uint32_t)mx.ldsa : PD_OOB;
+        }
+      } else {
+        so += a_tap * (int)mx.sw_tap;
+      }
+      BLDS4(rS, smem + 2 * KBUF + buf * SBUF + wave * 256, off, __builtin_amdgcn_readfirstlane(so));
+    }
+  };
   auto next_a = [&]() {
     if (++a_kc == kchunks) {
       a_kc = 0;
@@ -305,6 +386,7 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
   if (nk > 0) {
     issue_a(0, 0);
     issue_a(1, 0);
+    issue_s(0);
     next_a();
     issue_w(0);
     if (nk > 1) {
@@ -319,12 +401,14 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
   __builtin_amdgcn_sched_barrier(0);
 
   Frag256<F8> a[4], b0[2], b1[2];
+  [[maybe_unused]] int sa[4], sb0[2], sb1[2];      // MX: the lane's scale byte of each fragment
   // one quadrant: NR row tiles x 2 column tiles x K = 64 (two k-steps); consecutive MFMAs hit different accumulators
-#define QUAD16(NR, R0, C0, bfrag)                                                                                         \
+#define QUAD16(NR, R0, C0, bfrag, sbfrag)                                                                                 \
   if constexpr (F8) {                                                                                                     \
     _Pragma("unroll") for (int i = 0; i < (NR); ++i)                                                                      \
       _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                                       \
-        acc[(R0) + i][(C0) + c] = mfma_f8(a[i], bfrag[c], acc[(R0) + i][(C0) + c]);                                       \
+        if constexpr (MX) acc[(R0) + i][(C0) + c] = mfma_mx(a[i], bfrag[c], sa[i], sbfrag[c], acc[(R0) + i][(C0) + c]);   \
+        else acc[(R0) + i][(C0) + c] = mfma_f8(a[i], bfrag[c], acc[(R0) + i][(C0) + c]);                                  \
     /* pin the phase's MFMAs between its two barriers: without the anchors LLVM sinks the (side-effect free) intrinsic */  \
     /* calls of phases 0-2 past the barriers into phase 3 and the wave rows stop alternating (measured: 1.4x -> see DESIGN) */ \
     _Pragma("unroll") for (int i = 0; i < (NR); ++i)                                                                      \
@@ -356,16 +440,30 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
       for (int i = 0; i < RA0; ++i) a[i].load(sA + i * (16 * 128), lg, swz);
 #pragma unroll
       for (int c = 0; c < 2; ++c) b1[c].load(sB + (2 + c) * (16 * 128), lg, swz);
-      if (more1) { issue_a(0, cur ^ 1); issue_a(1, cur ^ 1); next_a(); }
+      if constexpr (MX) {
+        const char* sS = smem + cur * SBUF;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          sb0[c] = *(const uint8_t*)(sS + sr.rd_b + c * 64);
+          sb1[c] = *(const uint8_t*)(sS + sr.rd_b + (2 + c) * 64);
+        }
+#pragma unroll
+        for (int i = 0; i < RA0; ++i) sa[i] = *(const uint8_t*)(sS + sr.rd_a + i * 64);
+      }
+      if (more1) { issue_a(0, cur ^ 1); issue_a(1, cur ^ 1); issue_s(cur ^ 1); next_a(); }
       PHASE_SYNC();
       __builtin_amdgcn_s_setprio(1);
-      QUAD16(RA0, 0, 0, b0)
-      QUAD16(RA0, 0, 2, b1)
+      QUAD16(RA0, 0, 0, b0, sb0)
+      QUAD16(RA0, 0, 2, b1, sb1)
       __builtin_amdgcn_s_setprio(0);
       PHASE_SYNC();
       // ---------- phase B: A row tiles 4 .. RT-1; quadrants (A1, W1), (A1, W0); W of kt+2; wait for kt+1 ----------
 #pragma unroll
       for (int i = 0; i < RA1; ++i) a[i].load(sA + (RA0 + i) * (16 * 128), lg, swz);
+      if constexpr (MX) {
+#pragma unroll
+        for (int i = 0; i < RA1; ++i) sa[i] = *(const uint8_t*)(smem + cur * SBUF + sr.rd_a + (RA0 + i) * 64);
+      }
       if (more2) {
         issue_w(cur);
         VMCNT(4);
@@ -374,8 +472,8 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
       }
       PHASE_SYNC();
       __builtin_amdgcn_s_setprio(1);
-      QUAD16(RA1, RA0, 2, b1)
-      QUAD16(RA1, RA0, 0, b0)
+      QUAD16(RA1, RA0, 2, b1, sb1)
+      QUAD16(RA1, RA0, 0, b0, sb0)
       __builtin_amdgcn_s_setprio(0);
       PHASE_SYNC();
       continue;
@@ -388,7 +486,7 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
     if (more1) issue_a(0, cur ^ 1);
     PHASE_SYNC();
     __builtin_amdgcn_s_setprio(1);
-    QUAD16(RA0, 0, 0, b0)
+    QUAD16(RA0, 0, 0, b0, sb0)
     __builtin_amdgcn_s_setprio(0);
     PHASE_SYNC();
 
@@ -398,7 +496,7 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
     if (more1) { issue_a(1, cur ^ 1); next_a(); }
     PHASE_SYNC();
     __builtin_amdgcn_s_setprio(1);
-    QUAD16(RA0, 0, 2, b1)
+    QUAD16(RA0, 0, 2, b1, sb1)
     __builtin_amdgcn_s_setprio(0);
     PHASE_SYNC();
 
@@ -407,7 +505,7 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
     for (int i = 0; i < RA1; ++i) a[i].load(sA + (RA0 + i) * (16 * 128), lg, swz);
     PHASE_SYNC();
     __builtin_amdgcn_s_setprio(1);
-    QUAD16(RA1, RA0, 2, b1)
+    QUAD16(RA1, RA0, 2, b1, sb1)
     __builtin_amdgcn_s_setprio(0);
     PHASE_SYNC();
 
@@ -420,7 +518,7 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
     }
     PHASE_SYNC();
     __builtin_amdgcn_s_setprio(1);
-    QUAD16(RA1, RA0, 0, b0)
+    QUAD16(RA1, RA0, 0, b0, sb0)
     __builtin_amdgcn_s_setprio(0);
     PHASE_SYNC();
   }
@@ -458,6 +556,7 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p) {
   }
 #endif
 }
+
 
 
 // out = epilogue(sum over K-slices of the slabs), four columns per thread; same arithmetic as igemm_epilogue_rows
@@ -632,5 +731,46 @@ int pd_igemm256_launch(const pd_igemm_args& a, int kind, hipStream_t s) {
   if (a.debug_flags & 64) return kind == 0 ? launch256<0, 8, false, false, false>(a, s) : launch256<2, 8, false, false, false>(a, s);   // (A/B: four phases)
   return kind == 0 ? launch256<0, 8>(a, s) : launch256<2, 8>(a, s);
 }
+
+#if !PD_IS_F16
+// pd_igemm_mx (mx.hip validates): the MX instantiation, K-split (a.ksplit >= 2: slabs + igemm_splitk_reduce_kernel, as the e4m3 form) or whole
+template <int KIND, bool SK>
+static int launch256_mx(const pd_igemm_args& a, const MxK& mx, hipStream_t s) {
+  constexpr int lds = 2 * KBUF + 2 * SBUF;
+  static bool attr_set_dev[PD_MAX_DEVICES];
+  bool& attr_set = attr_set_dev[pd_cur_device()];
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)igemm256_kernel<KIND, 8, SK, true, false, true, false, true, MxK>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) {
+      pd_set_error("pd_igemm_mx: hipFuncSetAttribute(%d) failed: %s", lds, hipGetErrorString(e));
+      return PD_ERR_LAUNCH;
+    }
+    attr_set = true;
+  }
+  const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
+  hipLaunchKernelGGL((igemm256_kernel<KIND, 8, SK, true, false, true, false, true, MxK>), dim3(tiles, SK ? a.ksplit : 1, 1), dim3(512), lds, s, a, mx);
+  PD_CHECK_LAUNCH();
+  if (SK) {
+    const int64_t total = (int64_t)a.M * (a.N >> 2);
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(igemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, a);
+    PD_CHECK_LAUNCH();
+  }
+  return PD_OK;
+}
+
+int pd_igemm256_launch_mx(const pd_igemm_args& a, const pd_mx_operands& m, int kind, hipStream_t s) {
+  MxK mx;
+  mx.sa = m.a_scales;
+  mx.sw = m.w_scales;
+  mx.ldsa = m.ld_a_scales;
+  mx.ldsw = m.ld_w_scales;
+  mx.sw_tap = (uint32_t)m.w_scale_tap_stride;
+  mx.sa_bytes = (uint32_t)((int64_t)a.B * a.Ti * a.Hi * a.Wi * m.ld_a_scales);
+  mx.sw_bytes = (uint32_t)((int64_t)(a.taps - 1) * m.w_scale_tap_stride + (int64_t)a.N * m.ld_w_scales);
+  if (a.ksplit >= 2) return kind == 0 ? launch256_mx<0, true>(a, mx, s) : launch256_mx<2, true>(a, mx, s);
+  return kind == 0 ? launch256_mx<0, false>(a, mx, s) : launch256_mx<2, false>(a, mx, s);
+}
+#endif
 
 }  // namespace PD_NS

@@ -1,6 +1,7 @@
 // Normalisation / cast kernels: fp32 residual stream in, bf16 (hi[/lo]) GEMM operands out.  All HBM-bound:
 // one pass over the row (LayerNorm) or two passes over the sample (GroupNorm: stats, then apply+SiLU+cast).
 #include "common.h"
+#include "mx_quant.h"
 
 namespace PD_NS {
 
@@ -814,5 +815,173 @@ extern "C" int PD_ENTRY(cast_rows)(const float* x, pd_bf16* out, pd_bf16* out_lo
   PD_CHECK_LAUNCH();
   return PD_OK;
 }
+
+#if !PD_IS_F16
+// -------------------------------------------------------------------------------------------------
+// MX e4m3 outputs (the A operands of pd_igemm_mx): the two producers above with one E8M0 scale byte per 32 channels of a row beside
+// the payload.  Both own whole rows with four consecutive channels per lane, so a block is 8 consecutive lanes and its maximum three
+// shuffles: no extra pass over the tensor.  Separate kernels: the instantiations above stay as they are.
+// -------------------------------------------------------------------------------------------------
+// LayerNorm: one wave per row (the two-pass statistics of layernorm_kernel), NV float4 per lane
+template <int NV>
+__global__ void __launch_bounds__(256) layernorm_mx_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, uint8_t* __restrict__ out,
+                                                           uint8_t* __restrict__ scales, int64_t rows, int C, int ld_out, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float4 v[NV];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int c = j * 256 + lane * 4;
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < C) t = *(const float4*)(x + row * (int64_t)C + c);
+    v[j] = t;
+    s += (t.x + t.y) + (t.z + t.w);
+  }
+  const float mean = wave_sum(s) / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int c = j * 256 + lane * 4;
+    if (c < C) {
+      const float a = v[j].x - mean, b = v[j].y - mean, cc = v[j].z - mean, d = v[j].w - mean;
+      q += (a * a + b * b) + (cc * cc + d * d);
+    }
+  }
+  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int c = j * 256 + lane * 4;
+    if (c >= ld_out) continue;                       // (ld_out % 32 == 0: the 8 lanes of a block leave together)
+    float y[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c < C) {
+      const float4 g = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
+      y[0] = (v[j].x - mean) * rstd * g.x + be.x;
+      y[1] = (v[j].y - mean) * rstd * g.y + be.y;
+      y[2] = (v[j].z - mean) * rstd * g.z + be.z;
+      y[3] = (v[j].w - mean) * rstd * g.w + be.w;
+    }
+    int sb;
+    const uint32_t w = mx_quantize4(y, sb);
+    *(uint32_t*)(out + row * (int64_t)ld_out + c) = w;
+    if ((c & 31) == 0) scales[row * (int64_t)(ld_out >> 5) + (c >> 5)] = (uint8_t)sb;
+  }
+}
+
+extern "C" int pd_layernorm_mx(const float* x, const float* gamma, const float* beta, uint8_t* out, uint8_t* scales, int64_t rows, int C,
+                               int ld_out, float eps, pd_stream_t stream) {
+  PD_CHECK_ARG(x && gamma && beta && out && scales, "pd_layernorm_mx: null pointer");
+  PD_CHECK_ARG(C > 0 && (C & 31) == 0 && C <= 256 * LN_MAXV, "pd_layernorm_mx: C=%d must be a multiple of 32 (one scale per 32 channels) and <= %d", C,
+               256 * LN_MAXV);
+  PD_CHECK_ARG(ld_out >= C && (ld_out & 31) == 0 && ld_out <= ((C + 255) / 256) * 256,
+               "pd_layernorm_mx: ld_out=%d must be >= C, a multiple of 32 and within the last 256-column block", ld_out);
+  PD_CHECK_ARG((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && ((uintptr_t)out & 3) == 0, "pd_layernorm_mx: misaligned pointer");
+  if (rows <= 0) return PD_OK;
+  const int nv = (C + 255) / 256;
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  hipStream_t s = (hipStream_t)stream;
+#define PD_LNMX(NV) hipLaunchKernelGGL((layernorm_mx_kernel<NV>), grid, dim3(256), 0, s, x, gamma, beta, out, scales, rows, C, ld_out, eps)
+  if (nv <= 1) PD_LNMX(1);
+  else if (nv <= 2) PD_LNMX(2);
+  else if (nv <= 4) PD_LNMX(4);
+  else if (nv <= 8) PD_LNMX(8);
+  else PD_LNMX(16);
+#undef PD_LNMX
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
+// GroupNorm [-> scale-shift] [-> SiLU]: the apply pass of gn_apply_vec_kernel (same statistics prologue, same arithmetic) with an MX output
+__global__ void __launch_bounds__(256) gn_apply_mx_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, const float* __restrict__ ss_scale,
+                                                          const float* __restrict__ ss_shift, int ld_ss,
+                                                          const double* __restrict__ partials, uint8_t* __restrict__ out,
+                                                          uint8_t* __restrict__ scales, int S, int C, int G, int ld_out, float eps, int silu,
+                                                          int nchunk) {
+  __shared__ float smr[2 * 256];
+  __shared__ double spart[2 * 256];
+  const int b = blockIdx.y, chunk = blockIdx.x;
+  const int cpg = C / G;
+  const int tid = threadIdx.x;
+  const int LP = 256 / G;
+  if (tid < LP * G) {
+    const int g = tid % G, j = tid / G;
+    double ss = 0, qq = 0;
+    const double* pp = partials + (int64_t)b * nchunk * G * 2 + g * 2;
+    for (int k = j; k < nchunk; k += LP) { ss += pp[(int64_t)k * G * 2]; qq += pp[(int64_t)k * G * 2 + 1]; }
+    spart[tid * 2] = ss;
+    spart[tid * 2 + 1] = qq;
+  }
+  __syncthreads();
+  if (tid < G) {
+    double ss = 0, qq = 0;
+    for (int j = 0; j < LP; ++j) { ss += spart[(j * G + tid) * 2]; qq += spart[(j * G + tid) * 2 + 1]; }
+    const double cnt = (double)S * cpg, mean = ss / cnt;
+    double var = qq / cnt - mean * mean;
+    if (var < 0) var = 0;
+    smr[tid * 2] = (float)mean;
+    smr[tid * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
+  }
+  __syncthreads();
+  const int CV = C >> 2, RP = 256 / CV;
+  const int cv = tid % CV, rr = tid / CV, c = cv * 4, g = c / cpg;
+  const float mean = smr[g * 2], rstd = smr[g * 2 + 1];
+  float4 ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
+  float a[4] = {rstd * ga.x, rstd * ga.y, rstd * ga.z, rstd * ga.w};
+  float d[4] = {be.x - mean * a[0], be.y - mean * a[1], be.z - mean * a[2], be.w - mean * a[3]};
+  if (ss_scale) {
+    const float4 sc = *(const float4*)(ss_scale + (int64_t)b * ld_ss + c), sh = *(const float4*)(ss_shift + (int64_t)b * ld_ss + c);
+    const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { a[k] *= (1.f + scv[k]); d[k] = d[k] * (1.f + scv[k]) + shv[k]; }
+  }
+  const int r0 = chunk * GN_ROWS, r1 = min(S, r0 + GN_ROWS);
+  const int lds = ld_out >> 5, padv = (ld_out - C) >> 2;
+  for (int r = rr; r < r1 - r0; r += RP) {           // (the 8 lanes of a block share r: C % 32 == 0)
+    const int64_t row = (int64_t)b * S + r0 + r;
+    const float4 v = *(const float4*)(x + row * C + c);
+    float y[4] = {v.x * a[0] + d[0], v.y * a[1] + d[1], v.z * a[2] + d[2], v.w * a[3] + d[3]};
+    if (silu) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) y[k] = y[k] / (1.f + expf(-y[k]));      // (expf, not __expf: a rounding boundary of the payload is 2^-4 away)
+    }
+    int sb;
+    const uint32_t w = mx_quantize4(y, sb);
+    *(uint32_t*)(out + row * ld_out + c) = w;
+    if ((c & 31) == 0) scales[row * lds + (c >> 5)] = (uint8_t)sb;
+    for (int pc = cv; pc < padv; pc += CV) {         // pad columns [C, ld_out): zero payload, scale byte 0
+      *(uint32_t*)(out + row * ld_out + C + pc * 4) = 0u;
+      if ((pc & 7) == 0) scales[row * lds + ((C + pc * 4) >> 5)] = 0;
+    }
+  }
+}
+
+extern "C" int pd_groupnorm_silu_mx(const float* x, const float* gamma, const float* beta, const float* ss_scale, const float* ss_shift,
+                                    int ld_ss, double* partials, uint8_t* out, uint8_t* scales, int B, int S, int C, int G, int ld_out,
+                                    float eps, int silu, pd_stream_t stream) {
+  PD_CHECK_ARG(x && gamma && beta && partials && out && scales, "pd_groupnorm_silu_mx: null pointer");
+  PD_CHECK_ARG(G > 0 && C % G == 0 && (C & 31) == 0, "pd_groupnorm_silu_mx: bad C/G (%d,%d): C must be a multiple of 32 (one scale per 32 channels)", C, G);
+  PD_CHECK_ARG(ld_out >= C && (ld_out & 31) == 0 && ld_out - C < 128, "pd_groupnorm_silu_mx: ld_out=%d must be a multiple of 32 in [C, C + 128)", ld_out);
+  PD_CHECK_ARG((ss_scale == nullptr) == (ss_shift == nullptr), "pd_groupnorm_silu_mx: scale/shift must come together");
+  const int nchunk = pd_groupnorm_nchunk(S, C);
+  const int CV = C / 4, cpg = C / G;
+  const bool vec = CV <= 256 && (256 % CV == 0) && (cpg % 4 == 0) && G <= 256 &&
+                   (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && ((uintptr_t)out & 3) == 0 &&
+                   (!ss_scale || ((ld_ss % 4 == 0) && (((uintptr_t)ss_scale | (uintptr_t)ss_shift) & 15) == 0));
+  if (!vec) {
+    pd_set_error("pd_groupnorm_silu_mx: needs C/4 dividing 256 and 4 | C/G (C = %d, G = %d)", C, G);
+    return PD_ERR_UNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(gn_stats_vec_kernel, dim3(nchunk, B), dim3(256), 0, s, x, partials, S, C, G);
+  PD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(gn_apply_mx_kernel, dim3(nchunk, B), dim3(256), 0, s, x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, out, scales,
+                     S, C, G, ld_out, eps, silu, nchunk);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+#endif
 
 }  // namespace PD_NS

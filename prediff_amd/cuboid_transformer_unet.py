@@ -28,7 +28,8 @@ from torch import nn
 from . import _lib as L
 from .cuboid_geometry import attention_tables, relative_position_bias, relative_position_index
 from .engine import Act, HipEngine
-from .packing import pack_conv, pack_conv_fp8, pack_linear, pack_linear_fp8, pack_pair_block, pack_pair_ffn_split, pack_pair_vecs, pad64
+from .packing import (pack_conv, pack_conv_fp8, pack_conv_mx, pack_linear, pack_linear_fp8, pack_linear_mx, pack_pair_block, pack_pair_ffn_split,
+                      pack_pair_vecs, pad64, pad128)
 from .patterns import CuboidSelfAttentionPatterns
 
 
@@ -332,8 +333,8 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         # precision: "bf16" (throughput), "fp16" (the same engine on IEEE-half operands: TF32-class accuracy at the bf16 rate), "fp16x2" (IEEE-half
         # activations x hi + lo IEEE-half weights: two MFMA products, inside the 1e-3 bar; "fp16x2_lin": the same with the 3x3x3 convolutions
         # on one product), "fp32" (hi/lo split, fp32-class accuracy), "fp8_conv" (bf16 engine with e4m3 operands for the 3x3x3 convolutions)
-        # or "fp8" (e4m3 for the convolutions and the K >= 512 token linears)
-        self._init_engine(precision, ("bf16", "fp16", "fp16x2", "fp16x2_lin", "fp32", "fp8", "fp8_conv"))
+        # or "fp8" (e4m3 for the convolutions and the K >= 512 token linears); "mxfp8_conv" / "mxfp8": their MX (block-scaled) counterparts
+        self._init_engine(precision, ("bf16", "fp16", "fp16x2", "fp16x2_lin", "fp32", "fp8", "fp8_conv", "mxfp8", "mxfp8_conv"))
         # "fp16": every kernel of the "bf16" engine with IEEE half as the 16-bit operand type (the library's pd_f16_* builds): 11-bit
         # significands where bf16 has 8 -- the precision class of the reference's own GPU setting (float32_matmul_precision "high" = TF32,
         # scripts/prediff/sevirlr/prediff_sevirlr_v1.yaml:63) at the bf16 MFMA rate.  Range 65504: the packers saturate; everything that is
@@ -354,6 +355,12 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         # 6 % with the linears as well (tests/test_hip_configs.py prints both).
         self.fp8_conv = precision in ("fp8", "fp8_conv")
         self.fp8_linear = precision == "fp8"
+        # "mxfp8_conv": the bf16 engine with the TimeEmbedResBlock convolutions on MX operands -- OCP e4m3 payload with one E8M0 scale byte per
+        # 32 input channels of a row, written by GroupNorm -> SiLU itself (pd_groupnorm_silu_mx) and applied by the scaled MFMA (pd_igemm_mx):
+        # no per-tensor or per-layer activation scale.  "mxfp8": also the K >= 512 linears whose A operand a LayerNorm writes (qkv, FFN-1);
+        # linears fed by another kernel's epilogue (proj after the attention core, FFN-2 after the activation) stay 16-bit.
+        self.mx_conv = precision in ("mxfp8", "mxfp8_conv")
+        self.mx_linear = precision == "mxfp8"
         self.fp8_attn_core = True     # precision="fp8": q k^T and attn v of the un-fused attention layers on the fp8 MFMA (e4m3 q, k, v, P)
         self.precision_name = precision
         self.fuse_ffn = True          # bf16 mode: fused LN->FFN kernel where the shape allows (units <= 256)
@@ -538,7 +545,7 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
 
     # ------------------------------------------------------------------------------------------------ packing
     def _params_key(self, device):
-        return (self.fp8_conv, self.fp8_linear, self.w_fold, self.w_fold_conv3d) + super()._params_key(device)
+        return (self.fp8_conv, self.fp8_linear, self.mx_conv, self.mx_linear, self.w_fold, self.w_fold_conv3d) + super()._params_key(device)
 
     def _packers(self, P: Dict[str, object], device):
         """The per-module packing functions (writing into P): lin, conv, norm, resblock, stack.  `_pack` runs them over the whole
@@ -548,13 +555,16 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         def f32(t):
             return t.detach().float().contiguous().to(device)
 
-        def lin(name, m: nn.Linear, fp8_ok=False):
+        def lin(name, m: nn.Linear, fp8_ok=False, mx_ok=False):
             P[name + ".w"] = pack_linear(m.weight.to(device), split, dtype=self.op_dtype, fold=self.w_fold)
             P[name + ".b"] = f32(m.bias) if m.bias is not None else None
             # precision="fp8": the long-K token linears (K >= 512: the level >= 1 blocks) on e4m3 operands too -- pd_igemm's fp8 form needs
             # K % 128 == 0, and an e4m3-producing epilogue in front of it needs N % 8 == 0
             if fp8_ok and self.fp8_linear and m.in_features >= 512 and m.in_features % 128 == 0 and m.out_features % 8 == 0:
                 P[name + ".w8"] = pack_linear_fp8(m.weight.to(device))                   # (e4m3 (N, K), scale)
+            # precision="mxfp8": the long-K linears behind a LayerNorm on MX operands (pd_layernorm_mx / pd_igemm_mx: K % 32 == 0)
+            if mx_ok and self.mx_linear and m.in_features >= 512 and m.in_features % 32 == 0:
+                P[name + ".wmx"] = pack_linear_mx(m.weight.to(device), name)             # (e4m3 (N, pad128(K)), E8M0 (N, pad128(K) / 32))
 
         def conv(name, m):
             k3d = m.weight.dim() == 5 and tuple(m.weight.shape[2:]) == (3, 3, 3)
@@ -577,6 +587,13 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
                         P[name + cn + ".w8"] = pack_conv_fp8(cm.weight.to(device))      # (e4m3 (27, N, C), scale)
                         gnm = m.in_layers[0] if cn == ".conv1" else m.out_layers[0]
                         P[name + cn + ".a8s"] = self._fp8_act_scale(gnm.weight, gnm.bias, cn == ".conv2" and m.use_embed and m.use_scale_shift_norm)
+            if self.mx_conv:
+                # the library's conditions, mirrored as above: pd_groupnorm_silu_mx (C % 32 == 0, C/4 | 256, 4 | C/G, G <= 256)
+                for cn, cm, G in ((".conv1", m.in_layers[2], m.in_groups), (".conv2", m.out_layers[3], m.out_groups)):
+                    Cc = cm.in_channels
+                    if (Cc % 32 == 0 and (Cc // 4) <= 256 and 256 % (Cc // 4) == 0 and Cc % G == 0 and (Cc // G) % 4 == 0 and G <= 256
+                            and tuple(cm.weight.shape[2:]) == (3, 3, 3)):
+                        P[name + cn + ".wmx"] = pack_conv_mx(cm.weight.to(device), name + cn)     # (e4m3 (27, N, pad128(C)), E8M0 scales)
             if m.use_embed:
                 P[name + ".emb.w"], P[name + ".emb.b"] = f32(m.emb_layers[1].weight), f32(m.emb_layers[1].bias)
             if not isinstance(m.skip_connection, nn.Identity):
@@ -585,7 +602,7 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         def stack(name, blk: StackCuboidSelfAttentionBlock, level):
             for a, at in enumerate(blk.attn_l):
                 n = f"{name}.attn{a}"
-                norm(n + ".ln", at.norm); lin(n + ".qkv", at.qkv, fp8_ok=True)
+                norm(n + ".ln", at.norm); lin(n + ".qkv", at.qkv, fp8_ok=True, mx_ok=True)
                 if at.use_final_proj:
                     lin(n + ".proj", at.proj, fp8_ok=True)
                 vol = self._geom[level][a]["vol"]
@@ -595,7 +612,7 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
                     P[n + ".bias"] = torch.zeros(at.num_heads, vol, vol, device=device)
             for a, ff in enumerate(blk.ffn_l):
                 n = f"{name}.ffn{a}"
-                norm(n + ".ln", ff.layer_norm); lin(n + ".fc1", ff.ffn_1, fp8_ok=not ff.gated); lin(n + ".fc2", ff.ffn_2, fp8_ok=not ff.gated)
+                norm(n + ".ln", ff.layer_norm); lin(n + ".fc1", ff.ffn_1, fp8_ok=not ff.gated, mx_ok=not ff.gated); lin(n + ".fc2", ff.ffn_2, fp8_ok=not ff.gated)
                 if ff.gated:
                     lin(n + ".gate", ff.ffn_1_gate)
 
@@ -716,6 +733,14 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         """GroupNorm `gn` [-> scale-shift] -> SiLU as the A operand of convolution `conv`: e4m3 rows (value * the layer's activation scale)
         where the layer has an e4m3 weight record (precision="fp8" / "fp8_conv"), else 16-bit rows."""
         g, beta = P[gn + ".g"], P[gn + ".beta"]
+        if (conv + ".wmx") in P:
+            ld = pad128(C)
+            q = self._buf("gn.a.mx", (B * S, ld), torch.float8_e4m3fn, dev)
+            sc = self._buf("gn.a.mxs", (B * S, ld // 32), torch.uint8, dev)
+            part = self._buf("gn.part", (B * L.groupnorm_nchunk(S, C) * G * 2,), torch.float64, dev)
+            kw = dict(ss_scale=ss, ss_shift=ss[:, C:], ld_ss=2 * C) if ss is not None else {}
+            L.groupnorm_silu_mx(x, g, beta, part, q, sc, B, S, C, G, 1e-5, silu=True, **kw)
+            return Act(q, None, ld, None, sc)
         if (conv + ".w8") not in P:
             return self._groupnorm(x, g, beta, B, S, C, G, "gn.a", dev, 1e-5, ss=ss, opts=self._opts_for(B))
         scale = P[conv + ".a8s"]
@@ -725,9 +750,15 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         L.groupnorm_silu_fp8(x, g, beta, part, a8, B, S, C, G, 1e-5, scale, silu=True, **kw)
         return Act(a8, None, C, scale)
 
-    def _ln(self, P, name, x, rows, C, dev, fp8=False) -> Act:
-        """LayerNorm `name`.ln as a GEMM operand: 16-bit rows, or (fp8) e4m3 rows of value * 2^FP8_ACT_LOG2."""
+    def _ln(self, P, name, x, rows, C, dev, fp8=False, mx=False) -> Act:
+        """LayerNorm `name`.ln as a GEMM operand: 16-bit rows, (fp8) e4m3 rows of value * 2^FP8_ACT_LOG2, or (mx) an MX operand."""
         g, beta = P[name + ".ln.g"], P[name + ".ln.beta"]
+        if mx:
+            ld = pad128(C)
+            q = self._buf("ln.a.mx", (rows, ld), torch.float8_e4m3fn, dev)
+            sc = self._buf("ln.a.mxs", (rows, ld // 32), torch.uint8, dev)
+            L.layernorm_mx(x, g, beta, q, sc, rows, C)
+            return Act(q, None, ld, None, sc)
         if fp8:
             a8 = self._buf("ln.a8", (rows, C), torch.float8_e4m3fn, dev)
             scale = float(2 ** self.FP8_ACT_LOG2)
@@ -809,7 +840,7 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
                and tabs.get("tok_out") is None)
         k8 = self.FP8_ACT_LOG2 if fp8 else 0
         rows = B * S
-        a = self._ln(P, name, x, rows, C, dev, fp8=fp8)
+        a = self._ln(P, name, x, rows, C, dev, fp8=fp8, mx=(name + ".qkv.wmx") in P)      # (precision="mxfp8": the qkv launch on MX operands)
         if fp8:
             o = Act(self._buf("attn.o8", (rows, C), torch.float8_e4m3fn, dev), None, C, float(2 ** k8))
         else:
@@ -844,7 +875,7 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         ldh = pad64(Hd)
         # (not where the layer has e4m3 operands -- precision="fp8", K >= 512: measured at full resolution, 89.5 steps/s with the e4m3 FFN launches
         #  at level 1 vs 87.8 with this kernel there; bf16: 71.2 with it vs 69.0 without, profiles/r06_f_fullres_*.json)
-        if self.precision == "bf16" and self.fuse_ffn_rows and (name + ".rows") in P and ld == C and (name + ".fc1.w8") not in P:
+        if self.precision == "bf16" and self.fuse_ffn_rows and (name + ".rows") in P and ld == C and (name + ".fc1.w8") not in P and (name + ".fc1.wmx") not in P:
             wf, vecs, eps = P[name + ".rows"]
             L.ffn_rows(x, x, wf, vecs, B * S, C, eps, opts=self.opts)
             return
@@ -858,7 +889,7 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         fp8 = (name + ".fc1.w8") in P and (name + ".fc2.w8") in P and ld == C and ldh == Hd and not ff.gated
         k8 = self.FP8_ACT_LOG2 if fp8 else 0
         rows = B * S
-        a = self._ln(P, name, x, rows, C, dev, fp8=fp8)
+        a = self._ln(P, name, x, rows, C, dev, fp8=fp8, mx=(name + ".fc1.wmx") in P)      # (precision="mxfp8": FFN-1 on MX operands; FFN-2 stays 16-bit)
         if fp8:
             h = Act(self._buf("ffn.h8", (rows, Hd), torch.float8_e4m3fn, dev), None, Hd, float(2 ** k8))
         else:

@@ -10,11 +10,13 @@ from .packing import pad64
 
 class Act(NamedTuple):
     """A operand of a pd_igemm launch: rows of `ld` elements.  scale None: 16-bit rows, `lo` the low halves of the hi/lo engine (else
-    None).  scale a float: `hi` holds e4m3 rows of value * scale."""
+    None).  scale a float: `hi` holds e4m3 rows of value * scale.  mx a tensor: `hi` holds the e4m3 payload of an MX operand and `mx`
+    its E8M0 block scales (rows of ld / 32 bytes)."""
     hi: torch.Tensor
     lo: Optional[torch.Tensor]
     ld: int
     scale: Optional[float] = None
+    mx: Optional[torch.Tensor] = None
 
 
 class HipEngine:
@@ -86,7 +88,14 @@ class HipEngine:
     # ------------------------------------------------------------------------------------------------ the weight launch
     def _gemm(self, P, name, act, /, *, M, N, taps=1, geom=None, alpha=1.0, **epilogue):
         """One pd_igemm launch of `act` against the packed weight record of layer `name` in P (+ its bias): the e4m3 record `.w8` where
-        the operand is e4m3 (both tensor scales go into alpha), else `.w`.  `epilogue`: the other keywords of `_lib.igemm`."""
+        the operand is e4m3 (both tensor scales go into alpha), the MX record `.wmx` (pd_igemm_mx) where it is an MX operand, else `.w`.
+        `epilogue`: the other keywords of `_lib.igemm`."""
+        if act.mx is not None:
+            w, ws = P[name + ".wmx"]                        # (e4m3 payload, E8M0 block scales)
+            if epilogue.pop("out_bf16_lo", None) is not None or epilogue.pop("out_fp8_log2", 0):
+                raise L.PrediffHipError(f"{name}: an MX launch writes fp32 or bfloat16 rows only (no low halves, no e4m3 output)")
+            L.igemm_mx(act.hi, act.mx, w, ws, M=M, N=N, taps=taps, geom=geom, bias=P.get(name + ".b"), alpha=alpha, **epilogue, opts=self.opts)
+            return
         fp8 = act.scale is not None
         w, w2 = P[name + (".w8" if fp8 else ".w")]          # (e4m3 weights, their scale) | (hi, lo-or-None)
         folded = not fp8 and w.dim() == 3 and w.shape[0] == 2 * taps

@@ -118,6 +118,63 @@ def pack_linear_fp8(weight: torch.Tensor, k_pad: Optional[int] = None):
     return to_fp8(w, s), s
 
 
+# ---------------------------------------------------------------------------------------------------- MX (block-scaled e4m3) operands
+MX_BLOCK = 32            # K elements that share one E8M0 scale byte (OCP microscaling)
+
+
+def quantize_mx(x: torch.Tensor, ld: Optional[int] = None):
+    """fp32 rows (..., K) -> MX operand (payload (..., ld) float8_e4m3fn, scales (..., ld / 32) uint8), ld = pad128(K) by default.
+    The rule of DESIGN.md section 7 (tests/_mx_ref.py restates it in numpy, csrc/mx_quant.h on the device): per 32 consecutive
+    elements, scale byte = max(0, 127 + e) with e = floor(log2(amax)) - 8, one more where amax * 2^-e would exceed 448; payload =
+    e4m3(x * 2^-e), round to nearest even.  An all-zero block and the padding columns: scale byte 0, zero payload."""
+    K = x.shape[-1]
+    if K % MX_BLOCK:
+        raise ValueError(f"MX operands need K % {MX_BLOCK} == 0; got K = {K}")
+    ld = pad128(K) if ld is None else ld
+    xb = x.detach().float().reshape(*x.shape[:-1], K // MX_BLOCK, MX_BLOCK)
+    bits = xb.abs().amax(-1).contiguous().view(torch.int32)        # exponent field = floor(log2(amax)) + 127
+    sb = (((bits >> 23) & 0xFF) - 8 + ((bits & 0x7FFFFF) > 0x600000).to(torch.int32)).clamp_(min=0)
+    inv = ((254 - sb) << 23).to(torch.int32).view(torch.float32)   # 2^(127 - byte)
+    q = (xb * inv[..., None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).reshape(*x.shape[:-1], K)
+    payload = torch.zeros(*x.shape[:-1], ld, dtype=torch.uint8, device=x.device)
+    payload[..., :K] = q.view(torch.uint8)
+    scales = torch.zeros(*x.shape[:-1], ld // MX_BLOCK, dtype=torch.uint8, device=x.device)
+    scales[..., :K // MX_BLOCK] = sb.to(torch.uint8)
+    return payload.view(torch.float8_e4m3fn).contiguous(), scales.contiguous()
+
+
+def dequantize_mx(payload: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """The fp64 values an MX operand stands for (tests, error reports)."""
+    e = (scales.to(torch.float64) - 127.0).repeat_interleave(MX_BLOCK, dim=-1)
+    return payload.to(torch.float32).double() * torch.exp2(e)
+
+
+def _mx_refuse(name: str, k: int):
+    from ._lib import PrediffHipError          # (late: _lib imports this module)
+    raise PrediffHipError(f"{name}: MX operands need an input width that is a multiple of {MX_BLOCK} (one scale per {MX_BLOCK} consecutive "
+                          f"input channels); got {k}")
+
+
+def pack_linear_mx(weight: torch.Tensor, name: str = "linear"):
+    """nn.Linear weight (N, K) -> MX operand (payload (N, pad128(K)), scales (N, pad128(K) / 32)): blocks of 32 input channels."""
+    N, K = weight.shape
+    if K % MX_BLOCK:
+        _mx_refuse(name, K)
+    return quantize_mx(weight.detach().float())
+
+
+def pack_conv_mx(weight: torch.Tensor, name: str = "conv"):
+    """Conv weight (N, C, *kernel) -> MX operand (payload (taps, N, pad128(C)), scales (taps, N, pad128(C) / 32)), taps enumerated
+    kernel-index-major like pack_conv: a block is 32 consecutive input channels inside one tap."""
+    N, Cn = weight.shape[:2]
+    if Cn % MX_BLOCK:
+        _mx_refuse(name, Cn)
+    taps = 1
+    for k in weight.shape[2:]:
+        taps *= k
+    return quantize_mx(weight.detach().float().reshape(N, Cn, taps).permute(2, 0, 1).contiguous())
+
+
 # ---------------------------------------------------------------------------------------------------- (attention, FFN) pair kernel
 PAIR_CHUNK_BYTES = 32768          # csrc/pair_block.hip: 32 fragments of 1 KB
 PAIR_VEC_FLOATS = 3584          # units 256; 6144 at units 512
