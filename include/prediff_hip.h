@@ -328,6 +328,19 @@ int pd_dpmpp_2m_step(const float* zt, const float* eps, float* hist, const float
 int pd_dpmpp_2m_step_guided(const float* zt, const float* eps, float* hist, const float* shift, const float* coef5, float* out, int B,
                             int64_t per_sample, pd_stream_t stream);
 
+/* SDE-DPM-Solver++(2M) step (no reference implementation): pd_dpmpp_2m_step with a noise term.  Per sample, with the row
+ *   [a_t, c_x, c_d, w, c_n] of coef5 (B,5) fp32 (schedule.make_dpmpp_2m_sde_coefficients),
+ *   x0 and D as pd_dpmpp_2m_step ; out = c_x z + c_d D + c_n noise ; hist <- x0.
+ *   noise: fp32 like zt, unit normal draws; it is not read where c_n == 0 (eta = 0: it may hold anything, NaN included), and the result
+ *   there is pd_dpmpp_2m_step's bit for bit.  hist as in pd_dpmpp_2m_step.  out must not alias zt, eps, noise or hist. */
+int pd_dpmpp_2m_sde_step(const float* zt, const float* eps, const float* noise, float* hist, const float* coef5, float* out, int B,
+                         int64_t per_sample, pd_stream_t stream);
+
+/* Knowledge-alignment guided form: out = <pd_dpmpp_2m_sde_step> - gamma * shift, the subtraction last, so a zero shift gives
+ *   pd_dpmpp_2m_sde_step's result bit for bit.  coef6 (B,6) fp32 per sample: [a_t, c_x, c_d, w, c_n, gamma]; shift: fp32 like zt. */
+int pd_dpmpp_2m_sde_step_guided(const float* zt, const float* eps, const float* noise, float* hist, const float* shift, const float* coef6,
+                                float* out, int B, int64_t per_sample, pd_stream_t stream);
+
 /* Layout glue for the frame-wise VAE: fp32 NCHW <-> channels-last NHWC (taming/autoencoder_kl.py:80-113 callers,
  * latent_diffusion.py:361-380,423-432). */
 int pd_nchw_to_nhwc(const float* x, float* out, int N, int C, int HW, int ld_out, pd_stream_t stream);

@@ -148,6 +148,8 @@ _PROTOS = {
     "pd_ddim_step_guided": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_dpmpp_2m_step": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_dpmpp_2m_step_guided": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_dpmpp_2m_sde_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_dpmpp_2m_sde_step_guided": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -545,6 +547,24 @@ def dpmpp_2m_step_guided(zt, eps, hist, shift, coef5, out, B, per_sample):
                                                   ("coef5", coef5, 5 * B), ("out", out, n)))
     _check(lib().pd_dpmpp_2m_step_guided(ptr(zt), ptr(eps), ptr(hist), ptr(shift), ptr(coef5), ptr(out), B, per_sample, stream_ptr()),
            "pd_dpmpp_2m_step_guided")
+
+
+def dpmpp_2m_sde_step(zt, eps, noise, hist, coef5, out, B, per_sample):
+    """One SDE-DPM-Solver++(2M) step (coef5 rows: a_t, c_x, c_d, w, c_n); `noise` is read only where c_n != 0, `hist` is updated in place."""
+    n = B * per_sample
+    _check_step_operands("dpmpp_2m_sde_step", (("zt", zt, n), ("eps", eps, n), ("noise", noise, n), ("hist", hist, n),
+                                               ("coef5", coef5, 5 * B), ("out", out, n)))
+    _check(lib().pd_dpmpp_2m_sde_step(ptr(zt), ptr(eps), ptr(noise), ptr(hist), ptr(coef5), ptr(out), B, per_sample, stream_ptr()),
+           "pd_dpmpp_2m_sde_step")
+
+
+def dpmpp_2m_sde_step_guided(zt, eps, noise, hist, shift, coef6, out, B, per_sample):
+    """pd_dpmpp_2m_sde_step minus gamma * shift (coef6 rows: a_t, c_x, c_d, w, c_n, gamma)."""
+    n = B * per_sample
+    _check_step_operands("dpmpp_2m_sde_step_guided", (("zt", zt, n), ("eps", eps, n), ("noise", noise, n), ("hist", hist, n),
+                                                      ("shift", shift, n), ("coef6", coef6, 6 * B), ("out", out, n)))
+    _check(lib().pd_dpmpp_2m_sde_step_guided(ptr(zt), ptr(eps), ptr(noise), ptr(hist), ptr(shift), ptr(coef6), ptr(out), B, per_sample,
+                                             stream_ptr()), "pd_dpmpp_2m_sde_step_guided")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):

@@ -132,7 +132,7 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
     frame_score / aligned_frame_score (frame_score.SEVIRFrameScore: the MSE / MAE / SSIM of test_step, :937-965): updated with every
     sample where score / aligned_score are.
     **sample_kwargs go to ldm.sample unchanged: sampler="ddim", ddim_steps=..., eta=... or sampler="dpmpp_2m", steps=..., discretize=...,
-    lower_order_final=..., noise_tape=... (both branches run the sampler they name)."""
+    lower_order_final=..., noise_tape=... or sampler="dpmpp_2m_sde", steps=..., eta=... (both branches run the sampler they name)."""
     import numpy as np
     from .alignment import get_alignment_kwargs_avg_x
     lay, ev = cfg["layout"], cfg["eval"]

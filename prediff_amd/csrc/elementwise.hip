@@ -235,6 +235,52 @@ extern "C" int pd_dpmpp_2m_step_guided(const float* zt, const float* eps, float*
   return PD_OK;
 }
 
+// ---- SDE-DPM-Solver++(2M) step (schedule.make_dpmpp_2m_sde_coefficients) ----
+// dpmpp_2m_step_kernel with a noise term: rows (a_t, c_x, c_d, w, c_n[, gamma]) per sample, out = c_x z + c_d D + c_n n.  c_n is per
+// sample like w, so the `c_n != 0` test is wave-uniform; with c_n == 0 (eta = 0) the noise buffer is NOT read and the operations
+// are dpmpp_2m_step_kernel's in its order, so the result is pd_dpmpp_2m_step's bit for bit whatever the buffer holds.
+template <bool GUIDED, typename... Shift>
+__global__ void __launch_bounds__(256) dpmpp_2m_sde_step_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
+                                                                const float* __restrict__ noise, float* __restrict__ hist,
+                                                                const float* __restrict__ coef, float* __restrict__ out, int64_t per,
+                                                                const Shift* __restrict__... shift) {
+  static_assert(sizeof...(Shift) == (GUIDED ? 1 : 0), "the guided step takes one shift pointer, the un-guided none");
+  constexpr int NC = GUIDED ? 6 : 5;
+  const int b = blockIdx.y;
+  const float a_t = coef[b * NC], c_x = coef[b * NC + 1], c_d = coef[b * NC + 2], w = coef[b * NC + 3], c_n = coef[b * NC + 4];
+  const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t);
+  const bool second_order = w != 0.f, stochastic = c_n != 0.f;
+  const int64_t base = (int64_t)b * per;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
+    const float z = zt[base + i];
+    const float z0 = fmaf(-s1, eps[base + i], z) * r;
+    float d = z0;
+    if (second_order) d = fmaf(w, z0 - hist[base + i], z0);
+    float v = fmaf(c_d, d, c_x * z);
+    if (stochastic) v = fmaf(c_n, noise[base + i], v);
+    if constexpr (GUIDED) v = v - coef[b * NC + 5] * first_of(shift...)[base + i];
+    out[base + i] = v;
+    hist[base + i] = z0;
+  }
+}
+extern "C" int pd_dpmpp_2m_sde_step(const float* zt, const float* eps, const float* noise, float* hist, const float* coef5, float* out, int B,
+                                    int64_t per_sample, pd_stream_t stream) {
+  PD_CHECK_ARG(zt && eps && noise && hist && coef5 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_sde_step: bad args");
+  hipLaunchKernelGGL(dpmpp_2m_sde_step_kernel<false>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, hist,
+                     coef5, out, per_sample);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+extern "C" int pd_dpmpp_2m_sde_step_guided(const float* zt, const float* eps, const float* noise, float* hist, const float* shift,
+                                           const float* coef6, float* out, int B, int64_t per_sample, pd_stream_t stream) {
+  PD_CHECK_ARG(zt && eps && noise && hist && shift && coef6 && out && B > 0 && B <= 65535 && per_sample > 0,
+               "pd_dpmpp_2m_sde_step_guided: bad args");
+  hipLaunchKernelGGL((dpmpp_2m_sde_step_kernel<true, float>), dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise,
+                     hist, coef6, out, per_sample, shift);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
 // ---- NCHW <-> NHWC (fp32) ----
 __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ out, int N, int C, int HW, int ld) {
   const int64_t total = (int64_t)N * HW * ld;

@@ -75,7 +75,9 @@ def sample_ensemble(ldm, cond, num_members: int, base_seed: int = 0, sampler: st
                     lower_order_final: Optional[bool] = None) -> torch.Tensor:
     """Draw `num_members` samples for ONE context (cond["y"]: (1, T_in, H, W, C)) across all ranks of `group`.
     sampler="dpmpp_2m" takes `steps` (default 20), `discretize` and `lower_order_final` (LatentDiffusion.dpmpp_2m_sample_loop); it reads
-    draw 0 of each member's noise only.
+    draw 0 of each member's noise only.  sampler="dpmpp_2m_sde" takes the same keywords and `eta` (dpmpp_2m_sde_sample_loop); this
+    function's `eta` defaults to 0.0, which reaches that sampler as the deterministic solver: pass eta=1.0 for the stochastic one.  Its
+    step k reads draw 1 + k of each member's own generator, so a member does not depend on the batch split or the world size.
 
     Returns (num_members, T_out, H, W, C) on every rank.  `sample_fn(cond_batch, batch, noise_fn)` can replace the call into
     `ldm.sample` (used by the CPU gloo tests of the sharding logic)."""
@@ -107,6 +109,9 @@ def sample_ensemble(ldm, cond, num_members: int, base_seed: int = 0, sampler: st
             out = ldm.sample(cb, sampler="ddim", ddim_steps=ddim_steps, eta=eta, **kw)
         elif sampler == "dpmpp_2m":
             out = ldm.sample(cb, sampler="dpmpp_2m", steps=20 if steps is None else steps, discretize=discretize,
+                             lower_order_final=lower_order_final, **kw)
+        elif sampler == "dpmpp_2m_sde":
+            out = ldm.sample(cb, sampler="dpmpp_2m_sde", steps=20 if steps is None else steps, eta=eta, discretize=discretize,
                              lower_order_final=lower_order_final, **kw)
         else:
             out = ldm.sample(cb, timesteps=timesteps, **kw)

@@ -5,13 +5,13 @@ aligned_mean :592-596, apply_model :440-445, encode/decode_first_stage :423-438,
 
 Same constructor keywords and call conventions; what changes:
   * one denoising step = denoiser forward (HIP kernels) + ONE fused step-epilogue kernel (pd_ddpm_step / pd_ddim_step /
-    pd_dpmpp_2m_step)
+    pd_dpmpp_2m_step / pd_dpmpp_2m_sde_step)
     instead of ~10 elementwise launches; the per-step schedule scalars are gathered on the device from t;
   * the step (denoiser + epilogue) is captured once into a HIP graph per (batch, sampler) and replayed: the host loop
     only refreshes t / noise, so small batches are not launch-bound;
   * a DDIM sampler exists (the reference ships only the two schedule helpers): ``sample(...,
     sampler="ddim", ddim_steps=50, eta=0.)``, and a second-order multistep one, DPM-Solver++(2M): ``sample(..., sampler="dpmpp_2m",
-    steps=20, discretize="quad")``;
+    steps=20, discretize="quad")``, with a stochastic form, ``sampler="dpmpp_2m_sde", eta=1.0``;
   * of the training side, everything that needs no gradient is here (q_sample, forward / p_losses as loss VALUES, LitEma + ema_scope,
     validation_step); training_step raises: there is no backward pass through the HIP kernels.
 The knowledge-alignment hook (`set_alignment`) is honoured with the reference semantics; its gradient stays in
@@ -28,7 +28,7 @@ from .distributions import DiagonalGaussianDistribution
 from .ema import LitEma
 from .loss_eval import LossEvaluationMixin
 from .schedule import (make_beta_schedule, make_ddim_guidance_coefficients, make_ddim_sampling_parameters, make_ddim_timesteps,
-                       make_dpmpp_2m_coefficients, make_logsnr_timesteps, schedule_tables)
+                       make_dpmpp_2m_coefficients, make_dpmpp_2m_sde_coefficients, make_logsnr_timesteps, schedule_tables)
 
 
 def parse_layout_shape(layout: str) -> Dict[str, int]:
@@ -412,8 +412,8 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         shape = self.get_batch_latent_shape(B)
         st = dict(z=torch.zeros(shape, device=device), noise=torch.zeros(shape, device=device),
                   t=torch.zeros(B, dtype=torch.int64, device=device), out=torch.zeros(shape, device=device),
-                  coef=torch.zeros(B, 4 if kind == "dpmpp" else 3, device=device), zc=zc.detach().clone().float().contiguous())
-        if kind == "dpmpp":              # the previous step's x0; every loop's first step has w = 0 and does not read it
+                  coef=torch.zeros(B, {"dpmpp": 4, "dpmpp_sde": 5}.get(kind, 3), device=device), zc=zc.detach().clone().float().contiguous())
+        if kind in ("dpmpp", "dpmpp_sde"):   # the previous step's x0; every loop's first step has w = 0 and does not read it
             st["hist"] = torch.zeros(shape, device=device)
 
         def body():
@@ -426,6 +426,8 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                 self._ddpm_update(st["z"], eps, st["noise"], None, st["t"], 1.0, self.clip_denoised, out=st["out"])
             elif kind == "dpmpp":
                 L.dpmpp_2m_step(st["z"], eps, st["hist"], st["coef"], st["out"], B, st["z"][0].numel())
+            elif kind == "dpmpp_sde":
+                L.dpmpp_2m_sde_step(st["z"], eps, st["noise"], st["hist"], st["coef"], st["out"], B, st["z"][0].numel())
             else:
                 L.ddim_step(st["z"], eps, st["noise"], st["coef"], st["out"], B, st["z"][0].numel())
         torch.cuda.synchronize(device)          # no other lane is mid-replay while this one warms up / captures
@@ -716,16 +718,8 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                                  epilogue, coefs=coefs, draw="early" if eta > 0 else None, use_alignment=use_alignment, y=y,
                                  alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates)
 
-    @torch.no_grad()
-    @_on_own_device
-    def dpmpp_2m_sample_loop(self, cond, shape, steps=20, discretize="quad", lower_order_final=None, x_T=None, noise_tape=None,
-                             return_intermediates=False, use_alignment=False, alignment_kwargs=None, y=None):
-        """DPM-Solver++(2M), data prediction (DESIGN.md §7; not in the reference): a second-order multistep ODE solver, one denoiser
-        call per step like DDIM at eta = 0, keeping the previous step's x0 (schedule.make_dpmpp_2m_coefficients has the rule).
-        discretize: "quad" | "uniform" (make_ddim_timesteps) | "logsnr" (make_logsnr_timesteps); repeated grid points are dropped, so
-        fewer than `steps` steps may run.  Deterministic: only x_T, else noise_tape[0], else one device draw, is consumed.
-        use_alignment: z_prev -= gamma_idx * alignment_fn(z_t, steps[idx], zc=cond, y=y, **alignment_kwargs), gamma_idx as guided DDIM."""
-        B = shape[self.batch_axis]
+    def _dpmpp_grid(self, steps, discretize, use_alignment):
+        """What the two DPM-Solver++(2M) loops refuse, before any draw, then (alphas_cumprod as fp32 values in fp64, the grid)."""
         if self.shorten_cond_schedule:
             raise NotImplementedError("shorten_cond_schedule (num_timesteps_cond > 1) is defined for the ancestral loop only")
         if not (1 <= int(steps) <= self.num_timesteps):
@@ -740,6 +734,19 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         ac = self._alphas_cumprod_f64.astype(np.float32).astype(np.float64)
         grid = make_logsnr_timesteps(steps, ac) if discretize == "logsnr" else \
             np.minimum(make_ddim_timesteps(discretize, steps, self.num_timesteps), self.num_timesteps - 1)
+        return ac, grid
+
+    @torch.no_grad()
+    @_on_own_device
+    def dpmpp_2m_sample_loop(self, cond, shape, steps=20, discretize="quad", lower_order_final=None, x_T=None, noise_tape=None,
+                             return_intermediates=False, use_alignment=False, alignment_kwargs=None, y=None):
+        """DPM-Solver++(2M), data prediction (DESIGN.md §7; not in the reference): a second-order multistep ODE solver, one denoiser
+        call per step like DDIM at eta = 0, keeping the previous step's x0 (schedule.make_dpmpp_2m_coefficients has the rule).
+        discretize: "quad" | "uniform" (make_ddim_timesteps) | "logsnr" (make_logsnr_timesteps); repeated grid points are dropped, so
+        fewer than `steps` steps may run.  Deterministic: only x_T, else noise_tape[0], else one device draw, is consumed.
+        use_alignment: z_prev -= gamma_idx * alignment_fn(z_t, steps[idx], zc=cond, y=y, **alignment_kwargs), gamma_idx as guided DDIM."""
+        B = shape[self.batch_axis]
+        ac, grid = self._dpmpp_grid(steps, discretize, use_alignment)
         table, visited = make_dpmpp_2m_coefficients(ac, grid, lower_order_final)
         if use_alignment:      # a dropped grid point has an empty J and gamma 0: the visited steps' J still partition {0..grid[-1]}
             gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), grid)
@@ -767,13 +774,52 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
 
     @torch.no_grad()
     @_on_own_device
+    def dpmpp_2m_sde_sample_loop(self, cond, shape, steps=20, eta=1.0, discretize="quad", lower_order_final=None, x_T=None,
+                                 noise_tape=None, return_intermediates=False, use_alignment=False, alignment_kwargs=None, y=None):
+        """SDE-DPM-Solver++(2M) (not in the reference): dpmpp_2m_sample_loop's grid, visit list and x0 history with fresh
+        noise at every step (schedule.make_dpmpp_2m_sde_coefficients has the rule).  eta = 1 is the stochastic solver, whose
+        first-order member is DDIM at eta = 1; eta = 0 consumes x_T only and equals dpmpp_2m_sample_loop bit for bit.
+        Noise tape / RNG as ddim_sample_loop: x_T, then tape[1 + k] (or one whole-batch device draw) for visited step k when eta > 0.
+        use_alignment: as dpmpp_2m_sample_loop."""
+        B = shape[self.batch_axis]
+        ac, grid = self._dpmpp_grid(steps, discretize, use_alignment)
+        table, visited = make_dpmpp_2m_sde_coefficients(ac, grid, eta, lower_order_final)
+        if use_alignment:
+            gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), grid)
+            table = np.concatenate([table, gamma[visited, None]], axis=1)
+        # one row (a_t, c_x, c_d, w, c_n[, gamma]) per visited step, in visiting order
+        coefs = torch.tensor(table, dtype=torch.float32, device=self.betas.device)
+        stochastic = float(eta) > 0
+        if not stochastic:     # as dpmpp_2m_sample_loop: draw 0 is the only draw, and the driver gets no tape
+            x_T, noise_tape = self._start_latent(x_T, noise_tape, shape, self.betas.device), None
+        hist = []              # aligned / eager mode: one x0 history for the whole batch, owned by this call
+
+        def epilogue(cur, eps, shift, ts, row, noise):
+            if not hist:
+                hist.append(torch.empty_like(cur))
+            out = torch.empty_like(cur)
+            coef = coefs[row].expand(B, coefs.shape[1]).contiguous()
+            if noise is None:  # eta = 0: every c_n is 0 and the kernel does not read the buffer
+                noise = cur
+            with L.on_device(cur):
+                if shift is None:
+                    L.dpmpp_2m_sde_step(cur, eps, noise, hist[0], coef, out, B, cur[0].numel())
+                else:
+                    L.dpmpp_2m_sde_step_guided(cur, eps, noise, hist[0], shift, coef, out, B, cur[0].numel())
+            return out
+        return self._run_sampler("dpmpp_sde", cond, shape, x_T, noise_tape, [(int(grid[idx]), k) for k, idx in enumerate(visited)],
+                                 epilogue, coefs=coefs, draw="early" if stochastic else None, use_alignment=use_alignment, y=y,
+                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates)
+
+    @torch.no_grad()
+    @_on_own_device
     def sample(self, cond, batch_size=16, use_alignment=False, alignment_kwargs=None, return_intermediates=False, x_T=None,
                verbose=False, timesteps=None, mask=None, x0=None, shape=None, return_decoded=True, **kwargs):
-        """latent_diffusion.py:686-724.  Extra keywords (new API, consumed from **kwargs): sampler="ddpm"|"ddim"|"dpmpp_2m",
-        ddim_steps=50, eta=0.0, noise_tape=[x_T, n_1, ...]; with "dpmpp_2m": steps=20 (`ddim_steps` is accepted as an alias),
-        discretize="quad"|"uniform"|"logsnr", lower_order_final=None."""
+        """latent_diffusion.py:686-724.  Extra keywords (new API, consumed from **kwargs): sampler="ddpm"|"ddim"|"dpmpp_2m"|
+        "dpmpp_2m_sde", ddim_steps=50, eta=0.0, noise_tape=[x_T, n_1, ...]; with "dpmpp_2m" and "dpmpp_2m_sde": steps=20 (`ddim_steps` is
+        accepted as an alias), discretize="quad"|"uniform"|"logsnr", lower_order_final=None; "dpmpp_2m_sde" defaults to eta=1.0."""
         sampler = kwargs.pop("sampler", "ddpm")
-        ddim_steps, eta = kwargs.pop("ddim_steps", None), kwargs.pop("eta", 0.0)
+        ddim_steps, eta = kwargs.pop("ddim_steps", None), kwargs.pop("eta", 1.0 if sampler == "dpmpp_2m_sde" else 0.0)
         steps, discretize, lower_order_final = kwargs.pop("steps", None), kwargs.pop("discretize", "quad"), kwargs.pop("lower_order_final", None)
         noise_tape = kwargs.pop("noise_tape", None)
         if use_alignment:
@@ -806,6 +852,15 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             output = self.dpmpp_2m_sample_loop(zc, shape, steps=steps, discretize=discretize, lower_order_final=lower_order_final,
                                                x_T=x_T, noise_tape=noise_tape, return_intermediates=return_intermediates,
                                                use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y)
+        elif sampler == "dpmpp_2m_sde":
+            if mask is not None:
+                raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
+            if steps is None:
+                steps = 20 if ddim_steps is None else ddim_steps
+            output = self.dpmpp_2m_sde_sample_loop(zc, shape, steps=steps, eta=eta, discretize=discretize,
+                                                   lower_order_final=lower_order_final, x_T=x_T, noise_tape=noise_tape,
+                                                   return_intermediates=return_intermediates, use_alignment=use_alignment,
+                                                   alignment_kwargs=alignment_kwargs, y=y)
         else:
             output = self.p_sample_loop(cond=zc, shape=shape, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
                                         return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,

@@ -97,6 +97,23 @@ def make_logsnr_timesteps(num_steps, alphacums) -> np.ndarray:
     return steps.astype(np.int64)
 
 
+def _dpmpp_2m_visits(alphacums, timesteps, lower_order_final):
+    """(a, a_prev, h, w, visited) of the multistep solvers in fp64, in visiting order: the grid of make_ddim_sampling_parameters without
+    the points whose a_prev == a, h_k = lambda(a_prev) - lambda(a), w_k = h_{k-1} / (2 h_k) with w_0 = 0 and, with `lower_order_final`
+    (default: fewer than 15 visited steps), w_last = 0."""
+    _, a, a_prev = make_ddim_sampling_parameters(np.asarray(alphacums, dtype=np.float64), timesteps, 0.0)
+    visited = np.asarray([idx for idx in reversed(range(len(a))) if a_prev[idx] != a[idx]], dtype=np.int64)
+    a, a_prev = a[visited], a_prev[visited]
+    h = _half_logsnr(a_prev) - _half_logsnr(a)
+    w = np.zeros_like(h)
+    w[1:] = h[:-1] / (2.0 * h[1:])
+    if lower_order_final is None:
+        lower_order_final = len(visited) < 15
+    if lower_order_final and len(w):
+        w[-1] = 0.0
+    return a, a_prev, h, w, visited
+
+
 def make_dpmpp_2m_coefficients(alphacums, timesteps, lower_order_final=None):
     """DPM-Solver++(2M), data prediction (Lu et al. 2022, arXiv:2211.01095, algorithm 2), on the grid of make_ddim_sampling_parameters:
     a = alphacums[timesteps[idx]], a_prev = the grid point before it (alphacums[0] for idx = 0).  With alpha = sqrt(a),
@@ -108,19 +125,28 @@ def make_dpmpp_2m_coefficients(alphacums, timesteps, lower_order_final=None):
     (h = 0): it is dropped from the visit list and never enters h_{k-1}.
     Returns (table, visited): table[k] = (a, c_x, c_d, w_k) with c_x = sigma_prev / sigma and c_d = -alpha_prev expm1(-h_k), fp64
     from the alphacums as given, rounded to fp32 once; visited[k] = the grid index idx of the k-th visited step."""
-    _, a, a_prev = make_ddim_sampling_parameters(np.asarray(alphacums, dtype=np.float64), timesteps, 0.0)
-    visited = np.asarray([idx for idx in reversed(range(len(a))) if a_prev[idx] != a[idx]], dtype=np.int64)
-    a, a_prev = a[visited], a_prev[visited]
-    h = _half_logsnr(a_prev) - _half_logsnr(a)
-    w = np.zeros_like(h)
-    w[1:] = h[:-1] / (2.0 * h[1:])
-    if lower_order_final is None:
-        lower_order_final = len(visited) < 15
-    if lower_order_final and len(w):
-        w[-1] = 0.0
+    a, a_prev, h, w, visited = _dpmpp_2m_visits(alphacums, timesteps, lower_order_final)
     c_x = np.sqrt((1.0 - a_prev) / (1.0 - a))
     c_d = -np.sqrt(a_prev) * np.expm1(-h)
     return np.stack([a, c_x, c_d, w], axis=1).astype(np.float32), visited
+
+
+def make_dpmpp_2m_sde_coefficients(alphacums, timesteps, eta, lower_order_final=None):
+    """SDE-DPM-Solver++(2M) (Lu et al. 2022, arXiv:2211.01095) with the eta-generalisation in common use, midpoint form, on the grid,
+    the visit list and the h_k, w_k of make_dpmpp_2m_coefficients.  With unit noise n per visited step:
+        x0 = (z - sigma eps) / alpha;  D = x0 + w_k (x0 - x0_prev)
+        z_prev = (sigma_prev / sigma) exp(-eta h_k) z - alpha_prev expm1(-(1 + eta) h_k) D + sigma_prev sqrt(-expm1(-2 eta h_k)) n
+    eta = 0 is make_dpmpp_2m_coefficients' row element for element with c_n = 0; eta = 1 with w = 0 is the DDIM step at the sigma of
+    make_ddim_sampling_parameters(eta=1), the ancestral posterior on the grid.
+    Returns (table, visited): table[k] = (a, c_x, c_d, w_k, c_n), fp64 from the alphacums as given, rounded to fp32 once."""
+    eta = float(eta)
+    if not eta >= 0.0:
+        raise ValueError(f"eta must be >= 0, got {eta}")
+    a, a_prev, h, w, visited = _dpmpp_2m_visits(alphacums, timesteps, lower_order_final)
+    c_x = np.sqrt((1.0 - a_prev) / (1.0 - a)) * np.exp(-eta * h)
+    c_d = -np.sqrt(a_prev) * np.expm1(-(1.0 + eta) * h)
+    c_n = np.sqrt(1.0 - a_prev) * np.sqrt(-np.expm1(-2.0 * eta * h))
+    return np.stack([a, c_x, c_d, w, c_n], axis=1).astype(np.float32), visited
 
 
 def make_ddim_guidance_coefficients(posterior_log_variance_clipped, ddim_timesteps) -> np.ndarray:
