@@ -341,6 +341,21 @@ int pd_dpmpp_2m_sde_step(const float* zt, const float* eps, const float* noise, 
 int pd_dpmpp_2m_sde_step_guided(const float* zt, const float* eps, const float* noise, float* hist, const float* shift, const float* coef6,
                                 float* out, int B, int64_t per_sample, pd_stream_t stream);
 
+/* Tiled sampling on a canvas larger than the model's window (prediff_amd/tiled.py).  Channels-last fp32 throughout.
+ *   canvas (B, T, Hc, Wc, C); windows (B, nwin, T, h, w, C), batch-major; origin_yx (nwin, 2) int32 ON THE DEVICE, the (y, x) of each
+ *   window's first cell, 0 <= y <= Hc - h and 0 <= x <= Wc - w (the library cannot read the table: the caller checks it.  A window
+ *   whose origin is out of range is gathered as zeros and reads nothing; the blend never reads outside a window).
+ * pd_window_gather: windows[b, k] = canvas[b, :, y_k : y_k + h, x_k : x_k + w, :].
+ * pd_window_blend : canvas(cell) = sum over the windows k covering the cell, in ascending k, of weights[k, cell - origin_k] * windows[b, k,
+ *   cell - origin_k], accumulated with fmaf from 0 in fp32 by the one thread that owns the canvas element: no atomics, so two launches
+ *   agree bit for bit.  weights (nwin, h, w) fp32 arrive normalised (they sum to 1 over the windows that cover a cell); nothing is
+ *   divided on the device.  Every canvas element is written; a cell no window covers becomes 0.
+ * float4 access over C when C % 4 == 0 and both buffers are 16-byte aligned, scalar access otherwise. */
+int pd_window_gather(const float* canvas, float* windows, const int32_t* origin_yx, int B, int nwin, int T, int Hc, int Wc, int h, int w,
+                     int C, pd_stream_t stream);
+int pd_window_blend(const float* windows, const float* weights, const int32_t* origin_yx, float* canvas, int B, int nwin, int T, int Hc,
+                    int Wc, int h, int w, int C, pd_stream_t stream);
+
 /* Layout glue for the frame-wise VAE: fp32 NCHW <-> channels-last NHWC (taming/autoencoder_kl.py:80-113 callers,
  * latent_diffusion.py:361-380,423-432). */
 int pd_nchw_to_nhwc(const float* x, float* out, int N, int C, int HW, int ld_out, pd_stream_t stream);

@@ -150,6 +150,8 @@ _PROTOS = {
     "pd_dpmpp_2m_step_guided": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_dpmpp_2m_sde_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_dpmpp_2m_sde_step_guided": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_window_gather": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
+    "pd_window_blend": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -565,6 +567,68 @@ def dpmpp_2m_sde_step_guided(zt, eps, noise, hist, shift, coef6, out, B, per_sam
                                                       ("shift", shift, n), ("coef6", coef6, 6 * B), ("out", out, n)))
     _check(lib().pd_dpmpp_2m_sde_step_guided(ptr(zt), ptr(eps), ptr(noise), ptr(hist), ptr(shift), ptr(coef6), ptr(out), B, per_sample,
                                              stream_ptr()), "pd_dpmpp_2m_sde_step_guided")
+
+
+_origin_tables = {}      # (table bytes, canvas, window, device, covering) -> the checked device copy
+
+
+def window_origins(origins, canvas_hw, window_hw, device, covering=False):
+    """The device copy of a host origin table (nwin, 2) int32 of (y, x), checked once per (table, geometry, device) and kept: every window
+    lies inside the canvas, and with `covering` every canvas cell lies in some window.  The first call for a table uploads it (a
+    host-to-device copy); later calls, a graph capture's among them, only look it up."""
+    if origins.is_cuda or origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or origins.shape[0] < 1:
+        raise PrediffHipError(f"window origins must be a host int32 tensor (nwin, 2); got {origins.dtype} {tuple(origins.shape)} on {origins.device}")
+    (Hc, Wc), (h, w) = canvas_hw, window_hw
+    device = torch.device(device)
+    o = origins.contiguous().numpy()
+    key = (o.tobytes(), Hc, Wc, h, w, str(device), bool(covering))
+    dev = _origin_tables.get(key)
+    if dev is None:
+        if not (1 <= h <= Hc and 1 <= w <= Wc):
+            raise PrediffHipError(f"window {h} x {w} does not fit the canvas {Hc} x {Wc}")
+        if (o < 0).any() or (o[:, 0] > Hc - h).any() or (o[:, 1] > Wc - w).any():
+            raise PrediffHipError(f"window origins leave the canvas {Hc} x {Wc} (window {h} x {w}): {o.tolist()}")
+        if covering:
+            hit = torch.zeros(Hc, Wc, dtype=torch.bool)
+            for y, x in o.tolist():
+                hit[y:y + h, x:x + w] = True
+            if not bool(hit.all()):
+                raise PrediffHipError(f"window origins leave {int((~hit).sum())} of the {Hc} x {Wc} canvas cells uncovered")
+        dev = _origin_tables[key] = origins.contiguous().to(device)
+    return dev
+
+
+def _window_dims(fn, canvas, windows):
+    _dev(canvas, torch.float32), _dev(windows, torch.float32)
+    if canvas.dim() != 5 or windows.dim() != 6 or canvas.device != windows.device:
+        raise PrediffHipError(f"{fn}: canvas (B, T, Hc, Wc, C) and windows (B, nwin, T, h, w, C) on one device; got {tuple(canvas.shape)} "
+                              f"and {tuple(windows.shape)}")
+    B, T, Hc, Wc, Cn = canvas.shape
+    Bw, nwin, Tw, h, w, Cw = windows.shape
+    if (Bw, Tw, Cw) != (B, T, Cn):
+        raise PrediffHipError(f"{fn}: windows {tuple(windows.shape)} do not belong to the canvas {tuple(canvas.shape)}")
+    return B, nwin, T, Hc, Wc, h, w, Cn
+
+
+def window_gather(canvas, windows, origins):
+    """windows[b, k] = canvas[b, :, y_k : y_k + h, x_k : x_k + w, :] (pd_window_gather); origins: host int32 (nwin, 2), see window_origins."""
+    B, nwin, T, Hc, Wc, h, w, Cn = _window_dims("window_gather", canvas, windows)
+    if origins.shape[0] != nwin:
+        raise PrediffHipError(f"window_gather: {origins.shape[0]} origins for {nwin} windows")
+    table = window_origins(origins, (Hc, Wc), (h, w), canvas.device)
+    _check(lib().pd_window_gather(ptr(canvas), ptr(windows), ptr(table), B, nwin, T, Hc, Wc, h, w, Cn, stream_ptr()), "pd_window_gather")
+
+
+def window_blend(windows, weights, origins, canvas):
+    """canvas(cell) = sum over the covering windows, ascending, of weights[k] * windows[:, k] (pd_window_blend).  weights (nwin, h, w) fp32,
+    normalised; origins as window_gather, and refused when they leave a canvas cell uncovered."""
+    B, nwin, T, Hc, Wc, h, w, Cn = _window_dims("window_blend", canvas, windows)
+    _dev(weights, torch.float32)
+    if tuple(weights.shape) != (nwin, h, w) or weights.device != canvas.device or origins.shape[0] != nwin:
+        raise PrediffHipError(f"window_blend: weights {tuple(weights.shape)} / {origins.shape[0]} origins for {nwin} windows of {h} x {w}")
+    table = window_origins(origins, (Hc, Wc), (h, w), canvas.device, covering=True)
+    _check(lib().pd_window_blend(ptr(windows), ptr(weights), ptr(table), ptr(canvas), B, nwin, T, Hc, Wc, h, w, Cn, stream_ptr()),
+           "pd_window_blend")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):
