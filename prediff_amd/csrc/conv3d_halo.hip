@@ -334,18 +334,23 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
   const int m_end = min(p.M, m_base + 128);
   // accumulator register r of row tile i is MFMA row 4 lg + r; level 1: frame slot (4 lg + r) >> 3 of the wave row, pixel (i, (4 lg + r) & 7)
   const int c_row = L ? (lg >> 1) * 64 + (lg & 1) * 4 : 4 * lg;
-#pragma unroll
-  for (int js = 0; js < 2; ++js) {
-    __syncthreads();
+  // (one call per slab, not a loop: a loop the unroller declines, the epilogue being long, would index acc[] at run time -- scratch)
+  auto slab = [&](auto jsc) {
+    constexpr int js = decltype(jsc)::value;
+    // the slab aliases operand buffers that other waves may still read: one workgroup barrier; after it the slab is this wave's alone
+    if (js == 0) __syncthreads();
+    else igemm_epilogue_wave_sync();
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int r = 0; r < 4; ++r) sC[(c_row + i * (L ? 8 : 16) + r) * 32 + c * 16 + l16] = acc[i][js * 2 + c][r];
-    __syncthreads();
+    igemm_epilogue_wave_sync();
     igemm_epilogue<128, 32>(p, sC, lane, m_base, m_end, n0 + wc * 64 + js * 32, 0);
-  }
+  };
+  slab(std::integral_constant<int, 0>{});
+  slab(std::integral_constant<int, 1>{});
 #endif
 }
 

@@ -217,9 +217,11 @@ __global__ void __launch_bounds__(256, OCC) igemm_kernel(const pd_igemm_args p) 
   constexpr int WNS = WN / ESLAB;                  // columns staged at a time
   constexpr int TNS = TN16 / ESLAB;                // 16-column tiles staged at a time
   float* sC = (float*)smem + wave * (WM * WNS);
-#pragma unroll
-  for (int js = 0; js < ESLAB; ++js) {
-    __syncthreads();                               // operand stages (js == 0) / previous slab (js > 0) are no longer read
+  static_assert(ESLAB == 1 || ESLAB == 2, "one call per slab below");
+  auto slab = [&](auto jsc) {                      // (not a loop: one the unroller declines would index acc[] at run time -- scratch)
+    constexpr int js = decltype(jsc)::value;
+    if (js == 0) __syncthreads();                  // operand stages are no longer read by any wave; from here on the slab is this wave's alone
+    else igemm_epilogue_wave_sync();               // previous slab: read by this wave only
 #pragma unroll
     for (int i = 0; i < TM16; ++i)
 #pragma unroll
@@ -227,9 +229,11 @@ __global__ void __launch_bounds__(256, OCC) igemm_kernel(const pd_igemm_args p) 
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           sC[(i * 16 + 4 * lg + r) * WNS + j * 16 + l16] = acc[i][js * TNS + j][r];
-    __syncthreads();
-    igemm_epilogue<WM, WNS>(p, sC, lane, m0 + wr * WM, p.M, n0 + wc * WN + js * WNS, bz);
-  }
+    igemm_epilogue_wave_sync();
+    igemm_epilogue<WM, WNS, 4>(p, sC, lane, m0 + wr * WM, p.M, n0 + wc * WN + js * WNS, bz);
+  };
+  slab(std::integral_constant<int, 0>{});
+  if constexpr (ESLAB > 1) slab(std::integral_constant<int, 1>{});
 #endif
 }
 

@@ -533,27 +533,33 @@ __global__ void __launch_bounds__(512) igemm256_kernel(const pd_igemm_args p, co
   const int skip = wr == 1 ? SKIP1 : 0;
   const int m_base = m0 + wr * ROW1 + skip;
   const int m_end = min(p.M, m0 + (wr == 0 ? 16 * RT : BM));
-#pragma unroll
-  for (int js = 0; js < 2; ++js) {
-    __syncthreads();
+  // (one call per slab, not a loop: a loop the unroller declines, the epilogue being long, would index acc[] at run time -- scratch)
+  auto slab = [&](auto jsc) {
+    constexpr int js = decltype(jsc)::value;
+    // the slab aliases operand buffers that other waves may still read: one workgroup barrier; after it the slab is this wave's alone
+    if (js == 0) __syncthreads();
+    else igemm_epilogue_wave_sync();
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
       for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int r = 0; r < 4; ++r) sC[(i * 16 + 4 * lg + r) * 32 + c * 16 + l16] = acc[i][js * 2 + c][r];
-    __syncthreads();
+    igemm_epilogue_wave_sync();
     if (SK) {
       pd_igemm_args q = p;         // raw partial sums -> this slice's slab
       q.bias = nullptr; q.rowvec = nullptr; q.mul = nullptr; q.residual = nullptr; q.out_bf16 = nullptr; q.out_bf16_lo = nullptr;
       q.out_f32 = p.splitk_ws + (int64_t)kslice * p.M * p.N;
       q.ld_out = p.N; q.alpha = 1.f; q.act = 0; q.out_batch_stride = 0;
       q.vec_epilogue = (p.N & 3) == 0 ? 1 : 0;
-      igemm_epilogue<128, 32>(q, sC + skip * 32, lane, m_base, m_end, n0 + wc * 64 + js * 32, 0);
+      igemm_epilogue<128, 32, (SKIP1 > 0 ? 0 : PD_EPI_R)>(q, sC + skip * 32, lane, m_base, m_end, n0 + wc * 64 + js * 32, 0);
     } else {
-      igemm_epilogue<128, 32>(p, sC + skip * 32, lane, m_base, m_end, n0 + wc * 64 + js * 32, bz);
+      // (a slab that starts `skip` rows into the wave's 128 ends past them: such a tile form keeps the serial loop, which reads stored rows only)
+      igemm_epilogue<128, 32, (SKIP1 > 0 ? 0 : PD_EPI_R)>(p, sC + skip * 32, lane, m_base, m_end, n0 + wc * 64 + js * 32, bz);
     }
-  }
+  };
+  slab(std::integral_constant<int, 0>{});
+  slab(std::integral_constant<int, 1>{});
 #endif
 }
 

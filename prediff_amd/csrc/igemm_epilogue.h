@@ -121,8 +121,110 @@ __device__ __forceinline__ void igemm_epilogue_rows(const pd_igemm_args& p, cons
   }
 }
 
+// ---- the fp32 residual-stream writers, pipelined (the default; debug_flags bit 32 keeps the serial loop above for A/B runs) ----
+// The serial loop makes one HBM round trip per pass: vmcnt counts loads and stores alike and retires in order, so the wait for a pass's
+// operand load also waits for the previous pass's store.  Here a slab's passes go in batches of R: the operand loads of batch b + 1 are
+// issued before the LDS reads, the arithmetic and the R stores of batch b, so the counted wait of a load covers at most the stores of the
+// batch before the previous one, and a wave keeps up to 2 R loads + R stores in flight (< 63, the vmcnt field).  Per element the
+// operations and their order are those of the serial loop (fma(acc, alpha, bias), then + rowvec or + residual): the same bits.
+//  - A lane stores exactly the 16 B it loaded, in the pass it loaded them for: an in-place launch (residual == out_f32) stays correct.
+//  - Rows >= m_end are not stored; their operand loads read row m_end - 1 instead (no branch round a load: it would serialise the
+//    batch).  All WM rows of the slab are read, written by the caller or not: sC .. sC + WM * WNS must be the wave's own LDS.
+//  - m % res_period only when res_period != 0; the row vector once per slab when the slab lies inside one sample (UNI).
+#ifndef PD_EPI_R
+// Passes per batch.  4, 8 and 16 were built and measured (profiles/igemm_epilogue_ab.txt): none has scratch, and they time the same, in
+// the isolated Conv3d launches and in the headline -- with 4 the epilogue-only launch already moves its bytes at the HBM rate -- so the
+// one with the fewest registers stays: a wave has 8 loads + 4 stores of 1 KB in flight.  (-DPD_EPI_R=n builds another for A/B runs.)
+#define PD_EPI_R 4
+#endif
+template <int WM, int WNS, int RV, int RS, int R>
+__device__ __forceinline__ void igemm_epilogue_rows_f32(const pd_igemm_args& p, const float* sC, int lane, int m_base, int m_end, int n_base,
+                                                        float* outf, const float* res) {
+  static_assert(RV + RS == 1, "one global operand: the per-sample row vector or the residual");
+  constexpr int LPR = WNS / 4;                     // lanes per row
+  constexpr int RPP = 64 / LPR;                    // rows per pass
+  constexpr int NP = WM / RPP;                     // passes per slab
+  static_assert(NP % R == 0 && 3 * R < 63, "whole batches; loads + stores in flight fit the vmcnt field");
+  constexpr int NB = NP / R;
+  if (m_base >= m_end) return;
+  const int c0 = (lane % LPR) * 4;
+  const int row0 = lane / LPR;
+  const int n = n_base + c0;
+  const int m_last = m_end - 1;
+  float bias_v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) bias_v[e] = p.bias ? p.bias[n + e] : 0.f;
+  const float alpha = p.alpha;
+  auto run = [&](auto uni, auto full) {
+    constexpr bool UNI = decltype(uni)::value;       // one row vector for the whole slab
+    constexpr bool FULL = decltype(full)::value;     // every row of the slab is stored: no lane predicate round the stores
+    float4 rv0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (UNI) rv0 = *(const float4*)(p.rowvec + (int64_t)(m_base / p.rows_per_sample) * p.ld_rowvec + n);
+    auto issue = [&](int b, float4(&d)[R]) {
+      if (UNI) return;
+      int src[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) src[r] = FULL ? m_base + (b * R + r) * RPP + row0 : min(m_base + (b * R + r) * RPP + row0, m_last);
+      if (RS) {
+        if (p.res_period) {
+#pragma unroll
+          for (int r = 0; r < R; ++r) src[r] %= p.res_period;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) src[r] /= p.rows_per_sample;
+      }
+      const float* base = (RS ? res : p.rowvec) + n;
+      const int ld = RS ? p.ld_res : p.ld_rowvec;
+#pragma unroll
+      for (int r = 0; r < R; ++r) d[r] = *(const float4*)(base + (int64_t)src[r] * ld);
+    };
+    float4 g[2][R];
+    issue(0, g[0]);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      if (b + 1 < NB) issue(b + 1, g[(b + 1) & 1]);
+      float4 v[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) v[r] = *(const float4*)(sC + ((b * R + r) * RPP + row0) * WNS + c0);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float4 t4 = UNI ? rv0 : g[b & 1][r];
+        v[r].x = __builtin_fmaf(v[r].x, alpha, bias_v[0]) + t4.x;
+        v[r].y = __builtin_fmaf(v[r].y, alpha, bias_v[1]) + t4.y;
+        v[r].z = __builtin_fmaf(v[r].z, alpha, bias_v[2]) + t4.z;
+        v[r].w = __builtin_fmaf(v[r].w, alpha, bias_v[3]) + t4.w;
+        // the value exists here, for every lane: the arithmetic (and with it the counted wait for the operand load) must not sink into the
+        // predicated store below, where a lane-masked wait would be repeated, as vmcnt(0), in front of every later store
+        asm volatile("" : "+v"(v[r].x), "+v"(v[r].y), "+v"(v[r].z), "+v"(v[r].w));
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int m = m_base + (b * R + r) * RPP + row0;
+        if (FULL || m < m_end) *(float4*)(outf + (int64_t)m * p.ld_out + n) = v[r];
+      }
+    }
+  };
+  // (a partial slab's stores are predicated per lane; the waits the compiler counts across such a store assume it was not issued, so
+  // they retire some stores too: the full slab, which is every slab but the last rows of a launch, gets straight-line code)
+  const bool uni = RV && m_base / p.rows_per_sample == m_last / p.rows_per_sample;
+  const bool full = m_base + WM <= m_end;
+  if (RV && uni) {
+    if (full) run(std::true_type{}, std::true_type{});
+    else run(std::true_type{}, std::false_type{});
+  } else {
+    if (full) run(std::false_type{}, std::true_type{});
+    else run(std::false_type{}, std::false_type{});
+  }
+}
+
+// The slab of a wave is private to it and the LDS operations of one wave complete in order: between its slab writes and its row reads
+// (and between the reads of one slab and the writes of the next) a wave needs its own LDS wait, not a workgroup barrier.
+__device__ __forceinline__ void igemm_epilogue_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
 // sC: this wave's WM x WNS fp32 slab; (m_base, n_base): its position in the output; rows >= m_end are not stored; bz: batched-GEMM index.
-template <int WM, int WNS>
+// RMAX: the most passes per batch the calling kernel has registers for (no kernel may gain scratch); 0 = it keeps the serial loop.
+template <int WM, int WNS, int RMAX = PD_EPI_R>
 __device__ __forceinline__ void igemm_epilogue(const pd_igemm_args& p, const float* sC, int lane, int m_base, int m_end, int n_base, int bz) {
   float* outf = p.out_f32 ? p.out_f32 + (int64_t)bz * p.out_batch_stride : nullptr;
   pd_bf16* outb = p.out_bf16 ? p.out_bf16 + (int64_t)bz * p.outb_batch_stride : nullptr;
@@ -138,8 +240,17 @@ __device__ __forceinline__ void igemm_epilogue(const pd_igemm_args& p, const flo
     else igemm_epilogue_rows<WM, WNS, 8, GELU, 0, 0, 0, 0, 1, 0>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
   } else if (p.vec_epilogue && ofp && !obp && !mup && actv == 0 && (rsp != rvp)) {
     // fp32 residual-stream writers: proj / FFN-2 / conv-2 (+residual), conv-1 (+timestep embedding)
-    if (rsp) igemm_epilogue_rows<WM, WNS, 4, 0, 0, 0, 1, 1, 0, 0>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
-    else igemm_epilogue_rows<WM, WNS, 4, 0, 1, 0, 0, 1, 0, 0>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
+    // (pipelined unless debug_flags bit 32 asks for the serial loop; a lane whose four columns cross N takes the scalar path of that loop)
+    constexpr int NP = WM / (64 / (WNS / 4));
+    constexpr int R = RMAX == 0 ? 1 : RMAX < NP ? RMAX : NP;
+    const bool serial = RMAX == 0 || (p.debug_flags & 32) || n_base + (lane % (WNS / 4)) * 4 + 3 >= p.N;
+    if (rsp) {
+      if (serial) igemm_epilogue_rows<WM, WNS, 4, 0, 0, 0, 1, 1, 0, 0>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
+      else if (!(p.debug_flags & 2)) igemm_epilogue_rows_f32<WM, WNS, 0, 1, R>(p, sC, lane, m_base, m_end, n_base, outf, res);
+    } else {
+      if (serial) igemm_epilogue_rows<WM, WNS, 4, 0, 1, 0, 0, 1, 0, 0>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
+      else if (!(p.debug_flags & 2)) igemm_epilogue_rows_f32<WM, WNS, 1, 0, R>(p, sC, lane, m_base, m_end, n_base, outf, res);
+    }
   } else if (p.vec_epilogue == 2) {
     igemm_epilogue_rows<WM, WNS, 8, -1, 2, 2, 2, 2, 2, 2>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
   } else {
