@@ -356,6 +356,24 @@ int pd_window_gather(const float* canvas, float* windows, const int32_t* origin_
 int pd_window_blend(const float* windows, const float* weights, const int32_t* origin_yx, float* canvas, int B, int nwin, int T, int Hc,
                     int Wc, int h, int w, int C, pd_stream_t stream);
 
+/* Rolling forecasts beyond the model's horizon (DESIGN.md §7 "Rolling forecasts"; prediff_amd/rollout.py): the context advance between
+ *   two sampler runs, and the append of the kept frames, in one launch.  Channels-last fp32 throughout.
+ *   ctx, ctx_next: window stacks (B, nwin, T_in, h, w, C); z: the forecast latent canvas (B, T_out, Hc, Wc, C); origin_yx as above (a
+ *   window whose origin is out of range reads nothing from z and gets zeros for its new frames).  The plain module is nwin = 1,
+ *   (h, w) = (Hc, Wc), origin (0, 0).  1 <= stride <= T_out.
+ * With cat = [ctx ; z_scale * z] along T, ctx_next = cat[stride : stride + T_in] per window:
+ *   ctx_next[b, k, i] = ctx[b, k, i + stride]                                              where i + stride < T_in,
+ *   ctx_next[b, k, i] = z_scale * z[b, i + stride - T_in, y_k : y_k + h, x_k : x_k + w]    otherwise: ONE fp32 multiply per element
+ *   (z_scale = float32(1 / scale_factor), rounded by the caller; 1.0f makes it a copy).
+ * forecast (B, f_T, Hc, Wc, C), or NULL with f_cnt = 0: forecast[b, f_off + i] = z[b, i] for i < f_cnt <= T_out, unscaled, bit for bit;
+ *   f_off + f_cnt <= f_T.  Every element of ctx_next and of those f_cnt frames is written exactly once by one thread (no atomics); no
+ *   other element of either buffer is touched.  ctx_next and forecast must not overlap ctx, z or each other.  No synchronisation and
+ *   no host reads: the launch can be captured.
+ * float4 access over C when C % 4 == 0 and all five buffers are 16-byte aligned, scalar access otherwise; 64-bit element offsets. */
+int pd_context_advance(const float* ctx, const float* z, const int32_t* origin_yx, float* ctx_next, float* forecast, int B, int nwin,
+                       int T_in, int T_out, int Hc, int Wc, int h, int w, int C, int stride, float z_scale, int f_T, int f_off, int f_cnt,
+                       pd_stream_t stream);
+
 /* Layout glue for the frame-wise VAE: fp32 NCHW <-> channels-last NHWC (taming/autoencoder_kl.py:80-113 callers,
  * latent_diffusion.py:361-380,423-432). */
 int pd_nchw_to_nhwc(const float* x, float* out, int N, int C, int HW, int ld_out, pd_stream_t stream);

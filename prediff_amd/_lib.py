@@ -152,6 +152,7 @@ _PROTOS = {
     "pd_dpmpp_2m_sde_step_guided": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_window_gather": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
     "pd_window_blend": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),
+    "pd_context_advance": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.c_float] + [C.c_int] * 3 + [C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -629,6 +630,52 @@ def window_blend(windows, weights, origins, canvas):
     table = window_origins(origins, (Hc, Wc), (h, w), canvas.device, covering=True)
     _check(lib().pd_window_blend(ptr(windows), ptr(weights), ptr(table), ptr(canvas), B, nwin, T, Hc, Wc, h, w, Cn, stream_ptr()),
            "pd_window_blend")
+
+
+def _overlaps(a, b):
+    """whether the storage ranges of two contiguous tensors on one device intersect"""
+    pa, pb = a.data_ptr(), b.data_ptr()
+    return a.device == b.device and pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+
+def context_advance(ctx, z, origins, ctx_next, stride, z_scale, forecast=None, f_off=0, f_cnt=0):
+    """The context of the next segment of a rolling forecast, and the kept frames, in one launch (pd_context_advance):
+    ctx_next = cat([ctx, z_scale * z's windows], T)[:, :, stride : stride + T_in] and forecast[:, f_off : f_off + f_cnt] = z[:, : f_cnt].
+    ctx, ctx_next: (B, nwin, T_in, h, w, C); z: (B, T_out, Hc, Wc, C); origins: host int32 (nwin, 2), see window_origins; forecast:
+    (B, f_T, Hc, Wc, C), or None with f_cnt = 0.  z_scale is rounded to fp32 here."""
+    fn = "context_advance"
+    _dev(ctx, torch.float32), _dev(z, torch.float32), _dev(ctx_next, torch.float32)
+    if ctx.dim() != 6 or z.dim() != 5 or ctx_next.shape != ctx.shape or not (ctx.device == z.device == ctx_next.device):
+        raise PrediffHipError(f"{fn}: ctx and ctx_next (B, nwin, T_in, h, w, C) and z (B, T_out, Hc, Wc, C) on one device; got "
+                              f"{tuple(ctx.shape)}, {tuple(ctx_next.shape)} and {tuple(z.shape)}")
+    B, nwin, T_in, h, w, Cn = ctx.shape
+    Bz, T_out, Hc, Wc, Cz = z.shape
+    if (Bz, Cz) != (B, Cn) or origins.shape[0] != nwin:
+        raise PrediffHipError(f"{fn}: the windows {tuple(ctx.shape)} ({origins.shape[0]} origins) do not belong to the canvas {tuple(z.shape)}")
+    stride, f_off, f_cnt = int(stride), int(f_off), int(f_cnt)
+    if not 1 <= stride <= T_out:
+        raise PrediffHipError(f"{fn}: stride {stride} outside [1, T_out] = [1, {T_out}]")
+    outs = [("ctx_next", ctx_next)]
+    f_T = 0
+    if forecast is None:
+        if f_cnt != 0:
+            raise PrediffHipError(f"{fn}: f_cnt = {f_cnt} without a forecast buffer")
+    else:
+        _dev(forecast, torch.float32)
+        if forecast.dim() != 5 or forecast.device != z.device or (forecast.shape[0],) + tuple(forecast.shape[2:]) != (B, Hc, Wc, Cn):
+            raise PrediffHipError(f"{fn}: forecast must be (B, f_T, Hc, Wc, C) like z {tuple(z.shape)}; got {tuple(forecast.shape)}")
+        f_T = int(forecast.shape[1])
+        if f_cnt < 0 or f_off < 0 or f_cnt > T_out or f_off + f_cnt > f_T:
+            raise PrediffHipError(f"{fn}: forecast frames [{f_off}, {f_off} + {f_cnt}) do not fit f_T = {f_T} / T_out = {T_out}")
+        outs.append(("forecast", forecast))
+    for name, o in outs:
+        for other, t in (("ctx", ctx), ("z", z)) + tuple(p for p in outs if p[1] is not o):
+            if _overlaps(o, t):
+                raise PrediffHipError(f"{fn}: {name} overlaps {other}")
+    table = window_origins(origins, (Hc, Wc), (h, w), z.device)
+    _check(lib().pd_context_advance(ptr(ctx), ptr(z), ptr(table), ptr(ctx_next), ptr(forecast) if f_cnt else None, B, nwin, T_in, T_out,
+                                    Hc, Wc, h, w, Cn, stride, float(z_scale), f_T, f_off, f_cnt, stream_ptr()),
+           "pd_context_advance")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):

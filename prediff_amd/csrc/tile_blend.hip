@@ -7,13 +7,7 @@
 // The blend is a gather-form reduction: the thread that owns a canvas element walks the windows in ascending index, tests coverage
 // and accumulates fmaf(weight, value, acc) from acc = 0 -- no atomics, a fixed summation order, so two launches give the same bits.
 // The weights arrive normalised (they sum to 1 over the windows covering a cell; fp64 on the host, rounded once): nothing is divided here.
-#include "common.h"
-
-static inline unsigned grid_for(int64_t n) { return (unsigned)min((int64_t)8192, (n + 255) / 256); }
-
-template <int V> struct vec_of;
-template <> struct vec_of<1> { typedef float type; };
-template <> struct vec_of<4> { typedef float4 type; };
+#include "chan_vec.h"
 
 __device__ __forceinline__ void vfma(float g, float e, float& acc) { acc = fmaf(g, e, acc); }
 __device__ __forceinline__ void vfma(float g, const float4& e, float4& acc) {
@@ -22,8 +16,6 @@ __device__ __forceinline__ void vfma(float g, const float4& e, float4& acc) {
   acc.z = fmaf(g, e.z, acc.z);
   acc.w = fmaf(g, e.w, acc.w);
 }
-__device__ __forceinline__ void vzero(float& v) { v = 0.f; }
-__device__ __forceinline__ void vzero(float4& v) { v = make_float4(0.f, 0.f, 0.f, 0.f); }
 
 // Cv = C / V channel groups per cell.  A window whose origin lies outside [0, Hc - h] x [0, Wc - w] reads nothing and is written as zeros.
 template <int V>
@@ -79,8 +71,6 @@ __global__ void __launch_bounds__(256) window_blend_kernel(const float* __restri
     dst[i] = acc;
   }
 }
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 #define PD_CHECK_TILE_ARGS(name)                                                                                                   \
   PD_CHECK_ARG(canvas && windows && origin_yx && B > 0 && nwin > 0 && T > 0 && C > 0 && h > 0 && w > 0 && Hc >= h && Wc >= w,      \

@@ -811,21 +811,17 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                                  epilogue, coefs=coefs, draw="early" if stochastic else None, use_alignment=use_alignment, y=y,
                                  alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates)
 
-    @torch.no_grad()
-    @_on_own_device
-    def sample(self, cond, batch_size=16, use_alignment=False, alignment_kwargs=None, return_intermediates=False, x_T=None,
-               verbose=False, timesteps=None, mask=None, x0=None, shape=None, return_decoded=True, **kwargs):
-        """latent_diffusion.py:686-724.  Extra keywords (new API, consumed from **kwargs): sampler="ddpm"|"ddim"|"dpmpp_2m"|
-        "dpmpp_2m_sde", ddim_steps=50, eta=0.0, noise_tape=[x_T, n_1, ...]; with "dpmpp_2m" and "dpmpp_2m_sde": steps=20 (`ddim_steps` is
-        accepted as an alias), discretize="quad"|"uniform"|"logsnr", lower_order_final=None; "dpmpp_2m_sde" defaults to eta=1.0."""
+    @staticmethod
+    def _pop_sampler_kwargs(kwargs):
+        """The sampler keywords of `sample` (consumed from its **kwargs), with their defaults."""
         sampler = kwargs.pop("sampler", "ddpm")
-        ddim_steps, eta = kwargs.pop("ddim_steps", None), kwargs.pop("eta", 1.0 if sampler == "dpmpp_2m_sde" else 0.0)
-        steps, discretize, lower_order_final = kwargs.pop("steps", None), kwargs.pop("discretize", "quad"), kwargs.pop("lower_order_final", None)
-        noise_tape = kwargs.pop("noise_tape", None)
-        if use_alignment:
-            assert self.alignment_fn is not None, "Alignment function not set."
-        if shape is None:
-            shape = self.get_batch_latent_shape(batch_size=batch_size)
+        return dict(sampler=sampler, ddim_steps=kwargs.pop("ddim_steps", None), eta=kwargs.pop("eta", 1.0 if sampler == "dpmpp_2m_sde" else 0.0),
+                    steps=kwargs.pop("steps", None), discretize=kwargs.pop("discretize", "quad"),
+                    lower_order_final=kwargs.pop("lower_order_final", None))
+
+    def _latent_context(self, cond, batch_size):
+        """`sample`'s conditioning: (zc, y), the latent context the loops take (through cond_stage_forward when there is a condition
+        stage) and the caller's context as the alignment function sees it."""
         if self.cond_stage_model is not None:
             assert cond is not None
             if isinstance(cond, dict):
@@ -836,35 +832,58 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         else:
             zc = cond if isinstance(cond, torch.Tensor) else cond.get("y", None)
         y = cond if isinstance(cond, torch.Tensor) else cond.get("y", None)
+        return zc, y
+
+    def _sample_latent(self, zc, shape, y, *, sampler="ddpm", ddim_steps=None, eta=0.0, steps=None, discretize="quad",
+                       lower_order_final=None, timesteps=None, x_T=None, noise_tape=None, use_alignment=False, alignment_kwargs=None,
+                       return_intermediates=False, mask=None, x0=None, verbose=False):
+        """`sample`'s sampler dispatch on a latent context: the loop's output, undecoded (rollout.rollout_sample calls it per segment)."""
         if sampler == "ddim":
             if mask is not None:
                 raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
-            output = self.ddim_sample_loop(zc, shape, ddim_steps=50 if ddim_steps is None else ddim_steps, eta=eta, x_T=x_T,
-                                           noise_tape=noise_tape, return_intermediates=return_intermediates,
-                                           use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y)
-        elif sampler == "dpmpp_2m":
+            return self.ddim_sample_loop(zc, shape, ddim_steps=50 if ddim_steps is None else ddim_steps, eta=eta, x_T=x_T,
+                                         noise_tape=noise_tape, return_intermediates=return_intermediates,
+                                         use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y)
+        if sampler == "dpmpp_2m":
             if mask is not None:
                 raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
             if eta != 0.0:
                 raise NotImplementedError("DPM-Solver++(2M) is a deterministic ODE solver: eta must be 0")
             if steps is None:
                 steps = 20 if ddim_steps is None else ddim_steps
-            output = self.dpmpp_2m_sample_loop(zc, shape, steps=steps, discretize=discretize, lower_order_final=lower_order_final,
-                                               x_T=x_T, noise_tape=noise_tape, return_intermediates=return_intermediates,
-                                               use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y)
-        elif sampler == "dpmpp_2m_sde":
+            return self.dpmpp_2m_sample_loop(zc, shape, steps=steps, discretize=discretize, lower_order_final=lower_order_final,
+                                             x_T=x_T, noise_tape=noise_tape, return_intermediates=return_intermediates,
+                                             use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y)
+        if sampler == "dpmpp_2m_sde":
             if mask is not None:
                 raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
             if steps is None:
                 steps = 20 if ddim_steps is None else ddim_steps
-            output = self.dpmpp_2m_sde_sample_loop(zc, shape, steps=steps, eta=eta, discretize=discretize,
-                                                   lower_order_final=lower_order_final, x_T=x_T, noise_tape=noise_tape,
-                                                   return_intermediates=return_intermediates, use_alignment=use_alignment,
-                                                   alignment_kwargs=alignment_kwargs, y=y)
-        else:
-            output = self.p_sample_loop(cond=zc, shape=shape, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
-                                        return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
-                                        mask=mask, x0=x0, noise_tape=noise_tape)
+            return self.dpmpp_2m_sde_sample_loop(zc, shape, steps=steps, eta=eta, discretize=discretize,
+                                                 lower_order_final=lower_order_final, x_T=x_T, noise_tape=noise_tape,
+                                                 return_intermediates=return_intermediates, use_alignment=use_alignment,
+                                                 alignment_kwargs=alignment_kwargs, y=y)
+        return self.p_sample_loop(cond=zc, shape=shape, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
+                                  return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
+                                  mask=mask, x0=x0, noise_tape=noise_tape)
+
+    @torch.no_grad()
+    @_on_own_device
+    def sample(self, cond, batch_size=16, use_alignment=False, alignment_kwargs=None, return_intermediates=False, x_T=None,
+               verbose=False, timesteps=None, mask=None, x0=None, shape=None, return_decoded=True, **kwargs):
+        """latent_diffusion.py:686-724.  Extra keywords (new API, consumed from **kwargs): sampler="ddpm"|"ddim"|"dpmpp_2m"|
+        "dpmpp_2m_sde", ddim_steps=50, eta=0.0, noise_tape=[x_T, n_1, ...]; with "dpmpp_2m" and "dpmpp_2m_sde": steps=20 (`ddim_steps` is
+        accepted as an alias), discretize="quad"|"uniform"|"logsnr", lower_order_final=None; "dpmpp_2m_sde" defaults to eta=1.0."""
+        sampler_kwargs = self._pop_sampler_kwargs(kwargs)
+        noise_tape = kwargs.pop("noise_tape", None)
+        if use_alignment:
+            assert self.alignment_fn is not None, "Alignment function not set."
+        if shape is None:
+            shape = self.get_batch_latent_shape(batch_size=batch_size)
+        zc, y = self._latent_context(cond, batch_size)
+        output = self._sample_latent(zc, shape, y, timesteps=timesteps, x_T=x_T, noise_tape=noise_tape, use_alignment=use_alignment,
+                                     alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates, mask=mask, x0=x0,
+                                     verbose=verbose, **sampler_kwargs)
         if return_decoded:
             if return_intermediates:
                 samples, inter = output

@@ -274,12 +274,16 @@ class TiledLatentDiffusion(LatentDiffusion):
     def sample(self, cond, *args, **kwargs):
         """LatentDiffusion.sample on the canvas.  Refused before any draw: use_alignment, and a context that is not canvas-sized."""
         self._refuse_alignment(kwargs.get("use_alignment", args[1] if len(args) > 1 else False))
+        self._check_latent_context(cond)
+        return super().sample(cond, *args, **kwargs)
+
+    def _check_latent_context(self, cond):
+        """Without a condition stage the context is a latent canvas (also checked by rollout.rollout_sample)."""
         if self.cond_stage_model is None:
             zc = cond if isinstance(cond, torch.Tensor) else (cond.get("y") if isinstance(cond, dict) else None)
             if not isinstance(zc, torch.Tensor) or zc.dim() != 5 or tuple(zc.shape[2:4]) != self.geometry.canvas:
                 got = tuple(zc.shape) if isinstance(zc, torch.Tensor) else type(zc).__name__
                 raise ValueError(f"the latent context must be a canvas (B, T_in, {self.geometry.canvas[0]}, {self.geometry.canvas[1]}, C); got {got}")
-        return super().sample(cond, *args, **kwargs)
 
     p_sample = _refusing_alignment("p_sample")
     p_sample_loop = _refusing_alignment("p_sample_loop")
