@@ -197,7 +197,7 @@ class AutoencoderKL(nn.Module, HipEngine):
         G = self.norm_num_groups
         if self.precision == "bf16" and self.fuse_resblock and L.conv2d_gn_silu_supported(H, W, Cin, Cout, G) and pad64(Cin) == Cin:
             S = H * W
-            part = self._buf("gn.part", (N * L.groupnorm_nchunk(S, Cin) * G * 2,), torch.float64, dev)
+            part, _ = self._gn_args(N, S, Cin, G, dev)
             stats = self._buf("gn.stats", (N, G, 2), torch.float32, dev)
             L.groupnorm_stats(x, part, stats, N, S, Cin, G, VAE_EPS)
             L.conv2d_gn_silu(x, stats, P[gn_name + ".g"], P[gn_name + ".beta"], P[conv_name + ".w"][0], P[conv_name + ".b"], residual, out,

@@ -21,16 +21,21 @@ __device__ __forceinline__ float mx_block_max(float v) {
   return fmaxf(v, __shfl_xor(v, 4, 64));
 }
 
+// four fp32 -> four OCP e4m3 bytes of y * scale in one dword, saturating at +-448 (v_cvt_pk_fp8_f32 rounds to nearest even): the one e4m3
+// packer of the norm producers, unit-scale (norm.hip) and MX (below)
+__device__ __forceinline__ uint32_t pack_e4m3x4(const float (&y)[4], float scale) {
+  float q[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = fminf(fmaxf(y[k] * scale, -448.f), 448.f);
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], w, true);
+  return (uint32_t)w;
+}
+
 // this lane's four elements of a block -> four payload bytes (round to nearest even; the clamp never binds on finite input) and the block's
 // scale byte
 __device__ __forceinline__ uint32_t mx_quantize4(const float (&y)[4], int& scale_byte) {
   const float amax = mx_block_max(fmaxf(fmaxf(fabsf(y[0]), fabsf(y[1])), fmaxf(fabsf(y[2]), fabsf(y[3]))));
   scale_byte = mx_scale_byte(amax);
-  const float inv = mx_inv_scale(scale_byte);
-  float q[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = fminf(fmaxf(y[k] * inv, -448.f), 448.f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], w, true);
-  return (uint32_t)w;
+  return pack_e4m3x4(y, mx_inv_scale(scale_byte));
 }

@@ -1,9 +1,55 @@
-// Normalisation / cast kernels: fp32 residual stream in, bf16 (hi[/lo]) GEMM operands out.  All HBM-bound:
-// one pass over the row (LayerNorm) or two passes over the sample (GroupNorm: stats, then apply+SiLU+cast).
+// Normalisation / cast kernels: fp32 residual stream in, GEMM A operands out -- 16-bit (bf16 / fp16, or the bf16 hi/lo pair), unit-scale
+// e4m3 or MX e4m3.  All HBM-bound: one pass over the row (LayerNorm) or two passes over the sample (GroupNorm: stats, then
+// apply+SiLU+cast).  Every producer writes through the one writer family below; the statistics are shared per summation order.
 #include "common.h"
 #include "mx_quant.h"
 
 namespace PD_NS {
+
+// -------------------------------------------------------------------------------------------------
+// Output kinds and their writers.  `out` / `aux` are the bases of row-major buffers and row + c the element index of the first value
+// (row = the row's first element, c = the column: kept apart because a row is often wave-uniform):
+//   Op16  out = 16-bit operands (pack_op2 / f2op: the build's operand type); aux = the lo half of the bf16 hi/lo split, or null
+//   E4M3  out = bytes, e4m3(y * scale) saturating; aux unused
+//   MX    out = payload bytes, aux = E8M0 scale bytes, one per 32 elements (mx_quant.h states the format); the row length is a
+//         multiple of 32, so the element belongs to block (row >> 5) + (c >> 5) and the lane with c % 32 == 0 writes the block's byte
+// -------------------------------------------------------------------------------------------------
+enum class Out { Op16, E4M3, MX };
+
+__device__ __forceinline__ uint2 pack_op4(const float (&y)[4]) { return make_uint2(pack_op2(y[0], y[1]), pack_op2(y[2], y[3])); }
+
+// four consecutive values, one packed store per buffer (MX: the 8 lanes of a block call this together)
+template <Out OUT>
+__device__ __forceinline__ void write4(void* out, void* aux, int64_t row, int c, const float (&y)[4], float scale) {
+  const int64_t i = row + c;
+  if constexpr (OUT == Out::Op16) {
+    if (aux) {
+      uint16_t hi[4], lo[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) f2bf_split(y[k], hi[k], lo[k]);
+      *(uint2*)((pd_bf16*)out + i) = make_uint2(hi[0] | ((uint32_t)hi[1] << 16), hi[2] | ((uint32_t)hi[3] << 16));
+      *(uint2*)((pd_bf16*)aux + i) = make_uint2(lo[0] | ((uint32_t)lo[1] << 16), lo[2] | ((uint32_t)lo[3] << 16));
+    } else {
+      *(uint2*)((pd_bf16*)out + i) = pack_op4(y);
+    }
+  } else if constexpr (OUT == Out::E4M3) {
+    *(uint32_t*)((uint8_t*)out + i) = pack_e4m3x4(y, scale);
+  } else {
+    int sb;
+    *(uint32_t*)((uint8_t*)out + i) = mx_quantize4(y, sb);
+    if ((c & 31) == 0) ((uint8_t*)aux)[(row >> 5) + (c >> 5)] = (uint8_t)sb;
+  }
+}
+// one value (the scalar kernels: 16-bit outputs only)
+__device__ __forceinline__ void write1(pd_bf16* out, pd_bf16* out_lo, int64_t i, float y) {
+  if (out_lo) {
+    uint16_t hi, lo;
+    f2bf_split(y, hi, lo);
+    out[i] = hi; out_lo[i] = lo;
+  } else {
+    out[i] = f2op(y);
+  }
+}
 
 // -------------------------------------------------------------------------------------------------
 // LayerNorm over C (affine), one wave per row, two-pass in registers (exact mean / centered variance).
@@ -11,14 +57,19 @@ namespace PD_NS {
 // -------------------------------------------------------------------------------------------------
 constexpr int LN_MAXV = 16;   // up to 64*4*16 = 4096 channels per row
 
+// 1 / sqrt(var + eps): the only LayerNorm arithmetic that depends on the output kind.  The MX payload is compared byte for byte with
+// tests/_mx_ref.py, so its rstd is the IEEE quotient of the IEEE square root; the other kinds keep the faster rsqrtf.
+template <Out OUT>
+__device__ __forceinline__ float ln_rstd(float var_eps) { return OUT == Out::MX ? 1.0f / sqrtf(var_eps) : rsqrtf(var_eps); }
+
 // NV = float4 vectors per lane per row (ceil(C/256)), R = rows handled concurrently by one wave (independent load /
-// reduce chains keep R x NV 16 B loads in flight per lane: the kernel is pure HBM streaming).
-// F8: the output is OCP e4m3, value * fp8_scale, saturating (v_cvt_pk_fp8_f32 rounds to nearest even), one byte per channel.
-template <bool GATHER, int NV, int R, bool F8 = false>
+// reduce chains keep R x NV 16 B loads in flight per lane: the kernel is pure HBM streaming; MX runs R = 1).
+// OUT / out / aux / scale: see write4.  MX: ld_out % 32 == 0, so the 8 lanes of a block pass every branch below together.
+template <bool GATHER, int NV, int R, Out OUT>
 __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, pd_bf16* __restrict__ out,
-                                                        pd_bf16* __restrict__ out_lo, int64_t rows, int C, int ld_out,
-                                                        float eps, float fp8_scale,
+                                                        const float* __restrict__ beta, void* __restrict__ out,
+                                                        void* __restrict__ aux, int64_t rows, int C, int ld_out,
+                                                        float eps, float scale,
                                                         // patch-merge gather geometry (GATHER only)
                                                         int T, int H, int W, int Cs, int dt, int dh, int dw, int nearest) {
   const int lane = threadIdx.x & 63;
@@ -87,7 +138,7 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
     s[r] = q;
   }
 #pragma unroll
-  for (int r = 0; r < R; ++r) rstd[r] = rsqrtf(wave_sum(s[r]) / (float)C + eps);
+  for (int r = 0; r < R; ++r) rstd[r] = ln_rstd<OUT>(wave_sum(s[r]) / (float)C + eps);
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int c = j * 256 + lane * 4;
@@ -105,40 +156,39 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
         y[2] = (v[r][j].z - mean[r]) * rstd[r] * g.z + be.z;
         y[3] = (v[r][j].w - mean[r]) * rstd[r] * g.w + be.w;
       }
-      if (F8) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) y[k] = fminf(fmaxf(y[k] * fp8_scale, -448.f), 448.f);
-        int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], w, true);
-        *(int*)((uint8_t*)out + row * (int64_t)ld_out + c) = w;
-      } else if (out_lo) {
-        uint16_t hi[4], lo[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f2bf_split(y[k], hi[k], lo[k]);
-        *(uint2*)(out + row * (int64_t)ld_out + c) = make_uint2(hi[0] | ((uint32_t)hi[1] << 16), hi[2] | ((uint32_t)hi[3] << 16));
-        *(uint2*)(out_lo + row * (int64_t)ld_out + c) = make_uint2(lo[0] | ((uint32_t)lo[1] << 16), lo[2] | ((uint32_t)lo[3] << 16));
-      } else {
-        *(uint2*)(out + row * (int64_t)ld_out + c) =
-            make_uint2(pack_op2(y[0], y[1]), pack_op2(y[2], y[3]));
-      }
+      write4<OUT>(out, aux, row * (int64_t)ld_out, c, y, scale);
     }
   }
 }
 
-template <bool GATHER, bool F8 = false>
-static void launch_layernorm(const float* x, const float* gamma, const float* beta, pd_bf16* out, pd_bf16* out_lo, int64_t rows, int C,
-                             int ld_out, float eps, int T, int H, int W, int Cs, int dt, int dh, int dw, hipStream_t s, float fp8_scale = 0.f,
-                             int nearest = 0) {
+// One launcher for every LayerNorm entry point.  Rows per wave by vector count; MX keeps one row per wave.
+template <bool GATHER, Out OUT>
+static void launch_layernorm(const float* x, const float* gamma, const float* beta, void* out, void* aux, int64_t rows, int C, int ld_out,
+                             float eps, float scale, hipStream_t s, int T = 0, int H = 0, int W = 0, int Cs = 0, int dt = 1, int dh = 1,
+                             int dw = 1, int nearest = 0) {
   const int nv = (C + 255) / 256;
-#define PD_LN(NV, R)                                                                                                              \
-  hipLaunchKernelGGL((layernorm_kernel<GATHER, NV, R, F8>), dim3((unsigned)((rows + 4 * (R) - 1) / (4 * (R)))), dim3(256), 0, s, x, gamma, \
-                     beta, out, out_lo, rows, C, ld_out, eps, fp8_scale, T, H, W, Cs, dt, dh, dw, nearest)
+#define PD_LN(NV, RR)                                                                                                              \
+  do {                                                                                                                             \
+    constexpr int R = OUT == Out::MX ? 1 : (RR);                                                                                   \
+    hipLaunchKernelGGL((layernorm_kernel<GATHER, NV, R, OUT>), dim3((unsigned)((rows + 4 * R - 1) / (4 * R))), dim3(256), 0, s, x, gamma, \
+                       beta, out, aux, rows, C, ld_out, eps, scale, T, H, W, Cs, dt, dh, dw, nearest);                             \
+  } while (0)
   if (nv <= 1) PD_LN(1, 4);
   else if (nv <= 2) PD_LN(2, 2);
   else if (nv <= 4) PD_LN(4, 1);
   else if (nv <= 8) PD_LN(8, 1);
   else PD_LN(16, 1);
 #undef PD_LN
+}
+
+// C / ld_out of pd_layernorm, pd_layernorm_fp8 (mult = 4: a float4 per lane) and pd_layernorm_mx (mult = 32: one scale per 32 channels)
+static int ln_check_args(const char* who, int C, int ld_out, int mult) {
+  const bool mx = mult == 32;
+  PD_CHECK_ARG(C > 0 && C % mult == 0 && C <= 256 * LN_MAXV, "%s: C=%d must be a multiple of %d%s and <= %d", who, C, mult,
+               mx ? " (one scale per 32 channels)" : "", 256 * LN_MAXV);
+  PD_CHECK_ARG(ld_out >= C && ld_out % mult == 0 && ld_out <= ((C + 255) / 256) * 256,
+               "%s: ld_out=%d must be >= C, %smultiple of %d and within the last 256-column block", who, ld_out, mx ? "a " : "", mult);
+  return PD_OK;
 }
 
 #if !PD_IS_F16
@@ -155,11 +205,9 @@ extern "C" int PD_ENTRY(layernorm)(const float* x, const float* gamma, const flo
   PD_FORWARD_F16(PD_OPTS_F16(opts), pd_f16_layernorm(x, gamma, beta, out, out_lo, rows, C, ld_out, eps, opts, stream));
   PD_CHECK_ARG(!PD_IS_F16 || !out_lo, "pd_layernorm: the hi/lo split exists for bfloat16 operands only");
   PD_CHECK_ARG(x && gamma && beta && out, "pd_layernorm: null pointer");
-  PD_CHECK_ARG(C > 0 && (C & 3) == 0 && C <= 256 * LN_MAXV, "pd_layernorm: C=%d must be a multiple of 4 and <= %d", C, 256 * LN_MAXV);
-  PD_CHECK_ARG(ld_out >= C && (ld_out & 3) == 0 && ld_out <= ((C + 255) / 256) * 256,
-               "pd_layernorm: ld_out=%d must be >= C, multiple of 4 and within the last 256-column block", ld_out);
+  if (const int e = ln_check_args("pd_layernorm", C, ld_out, 4)) return e;
   if (rows <= 0) return PD_OK;
-  launch_layernorm<false>(x, gamma, beta, out, out_lo, rows, C, ld_out, eps, 0, 0, 0, 0, 1, 1, 1, (hipStream_t)stream);
+  launch_layernorm<false, Out::Op16>(x, gamma, beta, out, out_lo, rows, C, ld_out, eps, 0.f, (hipStream_t)stream);
   PD_CHECK_LAUNCH();
   return PD_OK;
 }
@@ -168,16 +216,25 @@ extern "C" int PD_ENTRY(layernorm)(const float* x, const float* gamma, const flo
 extern "C" int pd_layernorm_fp8(const float* x, const float* gamma, const float* beta, uint8_t* out, int64_t rows, int C, int ld_out,
                                 float eps, float fp8_scale, pd_stream_t stream) {
   PD_CHECK_ARG(x && gamma && beta && out && fp8_scale > 0.f, "pd_layernorm_fp8: null pointer / bad scale");
-  PD_CHECK_ARG(C > 0 && (C & 3) == 0 && C <= 256 * LN_MAXV, "pd_layernorm_fp8: C=%d must be a multiple of 4 and <= %d", C, 256 * LN_MAXV);
-  PD_CHECK_ARG(ld_out >= C && (ld_out & 3) == 0 && ld_out <= ((C + 255) / 256) * 256,
-               "pd_layernorm_fp8: ld_out=%d must be >= C, multiple of 4 and within the last 256-column block", ld_out);
+  if (const int e = ln_check_args("pd_layernorm_fp8", C, ld_out, 4)) return e;
   if (rows <= 0) return PD_OK;
-  launch_layernorm<false, true>(x, gamma, beta, (pd_bf16*)out, nullptr, rows, C, ld_out, eps, 0, 0, 0, 0, 1, 1, 1, (hipStream_t)stream,
-                                fp8_scale);
+  launch_layernorm<false, Out::E4M3>(x, gamma, beta, out, nullptr, rows, C, ld_out, eps, fp8_scale, (hipStream_t)stream);
   PD_CHECK_LAUNCH();
   return PD_OK;
 }
 
+// MX e4m3 rows (the A operand of pd_igemm_mx): one E8M0 scale byte per 32 channels of a row beside the payload.  A lane owns four
+// consecutive channels, so a block is 8 consecutive lanes and its maximum three shuffles: no extra pass over the tensor.
+extern "C" int pd_layernorm_mx(const float* x, const float* gamma, const float* beta, uint8_t* out, uint8_t* scales, int64_t rows, int C,
+                               int ld_out, float eps, pd_stream_t stream) {
+  PD_CHECK_ARG(x && gamma && beta && out && scales, "pd_layernorm_mx: null pointer");
+  if (const int e = ln_check_args("pd_layernorm_mx", C, ld_out, 32)) return e;
+  PD_CHECK_ARG((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && ((uintptr_t)out & 3) == 0, "pd_layernorm_mx: misaligned pointer");
+  if (rows <= 0) return PD_OK;
+  launch_layernorm<false, Out::MX>(x, gamma, beta, out, scales, rows, C, ld_out, eps, 0.f, (hipStream_t)stream);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
 #endif
 
 extern "C" int PD_ENTRY(patch_merge_layernorm_ex)(const float* x, const float* gamma, const float* beta, pd_bf16* out, pd_bf16* out_lo,
@@ -191,7 +248,8 @@ extern "C" int PD_ENTRY(patch_merge_layernorm_ex)(const float* x, const float* g
   PD_CHECK_ARG((C & 3) == 0 && Cm <= 256 * LN_MAXV, "pd_patch_merge_layernorm: C=%d (merged %d) unsupported", C, Cm);
   PD_CHECK_ARG(ld_out >= Cm && (ld_out & 3) == 0 && ld_out <= ((Cm + 255) / 256) * 256, "pd_patch_merge_layernorm: bad ld_out=%d", ld_out);
   const int64_t rows = (int64_t)B * ((T + dt - 1) / dt) * ((H + dh - 1) / dh) * ((W + dw - 1) / dw);
-  launch_layernorm<true>(x, gamma, beta, out, out_lo, rows, Cm, ld_out, eps, T, H, W, C, dt, dh, dw, (hipStream_t)stream, 0.f, pad_nearest ? 1 : 0);
+  launch_layernorm<true, Out::Op16>(x, gamma, beta, out, out_lo, rows, Cm, ld_out, eps, 0.f, (hipStream_t)stream, T, H, W, C, dt, dh, dw,
+                                    pad_nearest ? 1 : 0);
   PD_CHECK_LAUNCH();
   return PD_OK;
 }
@@ -278,6 +336,44 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__
   }
 }
 
+// ---- (sample, group) statistics from the per-chunk fp64 partial sums [chunk][g][sum, sum of squares].  Two summation orders, each kept
+// as it is (their fp64 totals, hence mean / rstd, can differ in the last bit):
+//   serial   one thread walks all chunks of its group: the scalar apply kernel and pd_groupnorm_stats
+//   striped  256 / G threads per group take every LP-th chunk, then one thread adds the LP sums: the vectorised apply kernel and the
+//            backward pass
+__device__ __forceinline__ float2 gn_mean_rstd(double sum, double sumsq, double cnt, float eps) {
+  const double mean = sum / cnt;
+  double var = sumsq / cnt - mean * mean;
+  if (var < 0) var = 0;
+  return make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
+}
+// serial order.  pb: this sample's (nchunk, G, 2) partial sums
+__device__ __forceinline__ float2 gn_stats_serial(const double* __restrict__ pb, int nchunk, int G, int g, double cnt, float eps) {
+  double ss = 0, qq = 0;
+  const double* pp = pb + g * 2;
+  for (int k = 0; k < nchunk; ++k) { ss += pp[(int64_t)k * G * 2]; qq += pp[(int64_t)k * G * 2 + 1]; }
+  return gn_mean_rstd(ss, qq, cnt, eps);
+}
+// striped order (G <= 256, 256 threads).  A single thread walking all the chunks is a chain of dependent L2 round trips -- 10+ us at 52
+// chunks, most of an apply kernel's time at small batches; the LP strided sums are added in a fixed order (deterministic).  True for the
+// threads tid < G, which hold group tid's totals; the caller stores what it derives from them and synchronises before reading it
+// (or before the next call on the same spart).
+__device__ __forceinline__ bool gn_reduce_partials(const double* __restrict__ pb, int nchunk, int G, double* spart, double& sum, double& sumsq) {
+  const int tid = threadIdx.x, LP = 256 / G;
+  if (tid < LP * G) {
+    const int g = tid % G, j = tid / G;
+    double a = 0, b = 0;
+    for (int k = j; k < nchunk; k += LP) { a += pb[((int64_t)k * G + g) * 2]; b += pb[((int64_t)k * G + g) * 2 + 1]; }
+    spart[tid * 2] = a;
+    spart[tid * 2 + 1] = b;
+  }
+  __syncthreads();
+  if (tid >= G) return false;
+  sum = sumsq = 0;
+  for (int j = 0; j < LP; ++j) { sum += spart[(j * G + tid) * 2]; sumsq += spart[(j * G + tid) * 2 + 1]; }
+  return true;
+}
+
 __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, const float* __restrict__ ss_scale,
                                                        const float* __restrict__ ss_shift, int ld_ss,
@@ -290,15 +386,9 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
   const int cpg = C / G;
   const int tid = threadIdx.x;
   for (int g = tid; g < G; g += 256) {
-    double ss = 0, qq = 0;
-    const double* pp = partials + (int64_t)b * nchunk * G * 2 + g * 2;
-    for (int k = 0; k < nchunk; ++k) { ss += pp[(int64_t)k * G * 2]; qq += pp[(int64_t)k * G * 2 + 1]; }
-    const double cnt = (double)S * cpg;
-    const double mean = ss / cnt;
-    double var = qq / cnt - mean * mean;
-    if (var < 0) var = 0;
-    smr[g * 2] = (float)mean;
-    smr[g * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    const float2 m = gn_stats_serial(partials + (int64_t)b * nchunk * G * 2, nchunk, G, g, (double)S * cpg, eps);
+    smr[g * 2] = m.x;
+    smr[g * 2 + 1] = m.y;
   }
   __syncthreads();
   const int r0 = chunk * GN_ROWS, r1 = min(S, r0 + GN_ROWS);
@@ -315,13 +405,7 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
       if (ss_scale) y = y * (1.f + ss_scale[(int64_t)b * ld_ss + c]) + ss_shift[(int64_t)b * ld_ss + c];
       if (silu) y = y / (1.f + expf(-y));
     }
-    if (obl) {
-      uint16_t hi, lo;
-      f2bf_split(y, hi, lo);
-      ob[i] = hi; obl[i] = lo;
-    } else {
-      ob[i] = f2op(y);
-    }
+    write1(ob, obl, i, y);
   }
 }
 
@@ -359,82 +443,72 @@ __global__ void __launch_bounds__(256) gn_stats_vec_kernel(const float* __restri
   }
 }
 
-// F8: the output is OCP e4m3, value * fp8_scale, saturating (v_cvt_pk_fp8_f32 rounds to nearest even), one byte per channel
-template <bool F8>
-__global__ void __launch_bounds__(256) gn_apply_vec_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, const float* __restrict__ ss_scale,
-                                                           const float* __restrict__ ss_shift, int ld_ss,
-                                                           const double* __restrict__ partials, pd_bf16* __restrict__ out,
-                                                           pd_bf16* __restrict__ out_lo, int S, int C, int G, float eps, int silu,
-                                                           int nchunk, float fp8_scale) {
-  __shared__ float smr[2 * 256];
-  __shared__ double spart[2 * 256];
-  const int b = blockIdx.y, chunk = blockIdx.x;
-  const int cpg = C / G;
-  const int tid = threadIdx.x;
-  // the sample's per-chunk partial sums: 256 / G threads per group take every LP-th chunk (a single thread walking all the
-  // chunks is a chain of dependent L2 round trips -- 10+ us at 52 chunks, most of this kernel's time at small batches), then one
-  // thread per group adds the LP strided sums in a fixed order (deterministic)
-  const int LP = 256 / G;
-  if (tid < LP * G) {
-    const int g = tid % G, j = tid / G;
-    double ss = 0, qq = 0;
-    const double* pp = partials + (int64_t)b * nchunk * G * 2 + g * 2;
-    for (int k = j; k < nchunk; k += LP) { ss += pp[(int64_t)k * G * 2]; qq += pp[(int64_t)k * G * 2 + 1]; }
-    spart[tid * 2] = ss;
-    spart[tid * 2 + 1] = qq;
-  }
-  __syncthreads();
-  if (tid < G) {
-    double ss = 0, qq = 0;
-    for (int j = 0; j < LP; ++j) { ss += spart[(j * G + tid) * 2]; qq += spart[(j * G + tid) * 2 + 1]; }
-    const double cnt = (double)S * cpg, mean = ss / cnt;
-    double var = qq / cnt - mean * mean;
-    if (var < 0) var = 0;
-    smr[tid * 2] = (float)mean;
-    smr[tid * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
-  __syncthreads();
-  const int CV = C >> 2, RP = 256 / CV;
-  const int cv = tid % CV, rr = tid / CV, c = cv * 4, g = c / cpg;
-  const float mean = smr[g * 2], rstd = smr[g * 2 + 1];
-  float4 ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
-  // fold: y = x * a + d  with a = rstd*gamma, d = beta - mean*rstd*gamma  [then (1+scale)*y + shift]
-  float a[4] = {rstd * ga.x, rstd * ga.y, rstd * ga.z, rstd * ga.w};
-  float d[4] = {be.x - mean * a[0], be.y - mean * a[1], be.z - mean * a[2], be.w - mean * a[3]};
+// The folded affine of four channels at c: y = x * a + d with a = rstd*gamma, d = beta - mean*rstd*gamma, then (1 + scale) * y + shift of sample b
+// folded in as well.  (Keep the address as base + row + c: as one 64-bit offset, gn_onepass_kernel<26, 512, 16> measured 2 % slower.)
+__device__ __forceinline__ void gn_affine_fold(const float* gamma, const float* beta, int c, const float* ss_scale, const float* ss_shift,
+                                               int b, int ld_ss, float mean, float rstd, float (&a)[4], float (&d)[4]) {
+  const float4 ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
+  a[0] = rstd * ga.x; a[1] = rstd * ga.y; a[2] = rstd * ga.z; a[3] = rstd * ga.w;
+  d[0] = be.x - mean * a[0]; d[1] = be.y - mean * a[1]; d[2] = be.z - mean * a[2]; d[3] = be.w - mean * a[3];
   if (ss_scale) {
     const float4 sc = *(const float4*)(ss_scale + (int64_t)b * ld_ss + c), sh = *(const float4*)(ss_shift + (int64_t)b * ld_ss + c);
     const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) { a[k] *= (1.f + scv[k]); d[k] = d[k] * (1.f + scv[k]) + shv[k]; }
   }
+}
+// ... applied to a float4 [-> SiLU].  EXACT_EXP: expf instead of __expf -- the MX output, where a rounding boundary of the payload is
+// 2^-4 away and the bytes are compared with a reference; every other output keeps the fast exponential.
+template <bool EXACT_EXP>
+__device__ __forceinline__ void gn_affine_silu4(const float4& v, const float (&a)[4], const float (&d)[4], int silu, float (&y)[4]) {
+  y[0] = v.x * a[0] + d[0]; y[1] = v.y * a[1] + d[1]; y[2] = v.z * a[2] + d[2]; y[3] = v.w * a[3] + d[3];
+  if (silu) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = y[k] / (1.f + (EXACT_EXP ? expf(-y[k]) : __expf(-y[k])));
+  }
+}
+
+// OUT / out / aux / scale: see write4.  Op16 and E4M3 rows are dense (ld_out is not read); MX rows have ld_out >= C columns, and the pad
+// columns [C, ld_out) get a zero payload and scale byte 0.
+template <Out OUT>
+__global__ void __launch_bounds__(256) gn_apply_vec_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, const float* __restrict__ ss_scale,
+                                                           const float* __restrict__ ss_shift, int ld_ss,
+                                                           const double* __restrict__ partials, void* __restrict__ out,
+                                                           void* __restrict__ aux, int S, int C, int G, int ld_out, float eps, int silu,
+                                                           int nchunk, float scale) {
+  __shared__ float smr[2 * 256];
+  __shared__ double spart[2 * 256];
+  const int b = blockIdx.y, chunk = blockIdx.x;
+  const int cpg = C / G;
+  const int tid = threadIdx.x;
+  double ss, qq;
+  if (gn_reduce_partials(partials + (int64_t)b * nchunk * G * 2, nchunk, G, spart, ss, qq)) {
+    const float2 m = gn_mean_rstd(ss, qq, (double)S * cpg, eps);
+    smr[tid * 2] = m.x;
+    smr[tid * 2 + 1] = m.y;
+  }
+  __syncthreads();
+  const int CV = C >> 2, RP = 256 / CV;
+  const int cv = tid % CV, rr = tid / CV, c = cv * 4, g = c / cpg;
+  float a[4], d[4];
+  gn_affine_fold(gamma, beta, c, ss_scale, ss_shift, b, ld_ss, smr[g * 2], smr[g * 2 + 1], a, d);
   const int r0 = chunk * GN_ROWS, r1 = min(S, r0 + GN_ROWS);
-  const float4* xb = (const float4*)(x + ((int64_t)b * S + r0) * C) + cv;
-  uint2* ob = (uint2*)(out + ((int64_t)b * S + r0) * C) + cv;
-  uint2* obl = out_lo ? (uint2*)(out_lo + ((int64_t)b * S + r0) * C) + cv : nullptr;
-  uint32_t* ob8 = (uint32_t*)((uint8_t*)out + ((int64_t)b * S + r0) * C) + cv;
-#pragma unroll 4
+  const int ld = OUT == Out::MX ? ld_out : C;
+  // (MX: the 8 lanes of a block share r, C % 32 == 0.  Its loop stays rolled: its registers and time are those of the rolled form)
+  constexpr int UNROLL = OUT == Out::MX ? 1 : 4;
+#pragma unroll UNROLL
   for (int r = rr; r < r1 - r0; r += RP) {
-    const float4 v = xb[(int64_t)r * CV];
-    float y[4] = {v.x * a[0] + d[0], v.y * a[1] + d[1], v.z * a[2] + d[2], v.w * a[3] + d[3]};
-    if (silu) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) y[k] = y[k] / (1.f + __expf(-y[k]));
-    }
-    if (F8) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) y[k] = fminf(fmaxf(y[k] * fp8_scale, -448.f), 448.f);
-      int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], w, true);
-      ob8[(int64_t)r * CV] = (uint32_t)w;
-    } else if (obl) {
-      uint16_t hi[4], lo[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) f2bf_split(y[k], hi[k], lo[k]);
-      ob[(int64_t)r * CV] = make_uint2(hi[0] | ((uint32_t)hi[1] << 16), hi[2] | ((uint32_t)hi[3] << 16));
-      obl[(int64_t)r * CV] = make_uint2(lo[0] | ((uint32_t)lo[1] << 16), lo[2] | ((uint32_t)lo[3] << 16));
-    } else {
-      ob[(int64_t)r * CV] = make_uint2(pack_op2(y[0], y[1]), pack_op2(y[2], y[3]));
+    const int64_t row = (int64_t)b * S + r0 + r;
+    float y[4];
+    gn_affine_silu4<OUT == Out::MX>(*(const float4*)(x + row * C + c), a, d, silu, y);
+    write4<OUT>(out, aux, row * ld, c, y, scale);
+    if constexpr (OUT == Out::MX) {
+      const int padv = (ld_out - C) >> 2;
+      for (int pc = cv; pc < padv; pc += CV) {
+        *(uint32_t*)((uint8_t*)out + row * ld + C + pc * 4) = 0u;
+        if ((pc & 7) == 0) ((uint8_t*)aux)[(row * ld + C + pc * 4) >> 5] = 0;
+      }
     }
   }
 }
@@ -521,23 +595,14 @@ __global__ void __launch_bounds__(NT) gn_onepass_kernel(const float* __restrict_
     pp[1] = ((double)var + (double)mean * (double)mean) * (double)cnt;
     for (int k = 1; k < nchunk; ++k) { pp[(int64_t)k * G * 2] = 0.0; pp[(int64_t)k * G * 2 + 1] = 0.0; }
   }
-  const float4 ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
-  float a[4] = {rstd * ga.x, rstd * ga.y, rstd * ga.z, rstd * ga.w};
-  float d[4] = {be.x - mean * a[0], be.y - mean * a[1], be.z - mean * a[2], be.w - mean * a[3]};
-  if (ss_scale) {
-    const float4 sc = *(const float4*)(ss_scale + (int64_t)b * ld_ss + c), sh = *(const float4*)(ss_shift + (int64_t)b * ld_ss + c);
-    const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { a[k] *= (1.f + scv[k]); d[k] = d[k] * (1.f + scv[k]) + shv[k]; }
-  }
+  float a[4], d[4];
+  gn_affine_fold(gamma, beta, c, ss_scale, ss_shift, b, ld_ss, mean, rstd, a, d);
 #pragma unroll
   for (int i = 0; i < RMAX; ++i) {
-    float y[4] = {v[i].x * a[0] + d[0], v[i].y * a[1] + d[1], v[i].z * a[2] + d[2], v[i].w * a[3] + d[3]};
-    if (silu) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) y[k] = y[k] / (1.f + __expf(-y[k]));
-    }
-    const u32x2_t o = {pack_op2(y[0], y[1]), pack_op2(y[2], y[3])};
+    float y[4];
+    gn_affine_silu4<false>(v[i], a, d, silu, y);
+    const uint2 p = pack_op4(y);
+    const u32x2_t o = {p.x, p.y};
     __builtin_amdgcn_raw_buffer_store_b64(o, rO, rl + RP * i < S ? voff >> 1 : GN_OOB, ((uint32_t)i * sstep) >> 1, 0);
     if ((i & 1) == 1) __builtin_amdgcn_sched_barrier(0);      // (two rows at a time: an unbounded interleave of the 35 rows spilled)
   }
@@ -566,6 +631,31 @@ static void gn_onepass_launch(const float* x, const float* gamma, const float* b
 #undef GN1P
 }
 
+// Shapes and pointers of the vectorised kernels (gn_stats_vec_kernel, gn_apply_vec_kernel): a thread owns one float4 column of ONE group,
+// 256 threads hold whole rows.  gamma / beta / scale-shift may be null where the caller has none.  The output's own conditions (alignment
+// of its packed store, dense rows) are the caller's.
+static bool gn_vec_ok(int C, int G, const float* x, const float* gamma, const float* beta, const float* ss_scale, const float* ss_shift,
+                      int ld_ss) {
+  if (C % 4 != 0) return false;
+  const int CV = C / 4, cpg = C / G;
+  return CV <= 256 && (256 % CV == 0) && (cpg % 4 == 0) && G <= 256 && (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 &&
+         (!ss_scale || ((ld_ss % 4 == 0) && (((uintptr_t)ss_scale | (uintptr_t)ss_shift) & 15) == 0));
+}
+
+// The two launches (statistics, apply) behind pd_groupnorm_silu's vectorised branch, pd_groupnorm_silu_fp8 and pd_groupnorm_silu_mx
+template <Out OUT>
+static int gn_two_pass(const float* x, const float* gamma, const float* beta, const float* ss_scale, const float* ss_shift, int ld_ss,
+                       double* partials, void* out, void* aux, int B, int S, int C, int G, int ld_out, float eps, int silu, float scale,
+                       hipStream_t s) {
+  const int nchunk = pd_groupnorm_nchunk(S, C);
+  hipLaunchKernelGGL(gn_stats_vec_kernel, dim3(nchunk, B), dim3(256), 0, s, x, partials, S, C, G);
+  PD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(gn_apply_vec_kernel<OUT>, dim3(nchunk, B), dim3(256), 0, s, x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, out, aux,
+                     S, C, G, ld_out, eps, silu, nchunk, scale);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
 extern "C" int PD_ENTRY(groupnorm_silu)(const float* x, const float* gamma, const float* beta, const float* ss_scale,
                                         const float* ss_shift, int ld_ss, double* partials, pd_bf16* out, pd_bf16* out_lo, int B, int S,
                                         int C, int G, int ld_out, float eps, int silu, const pd_call_opts* opts, pd_stream_t stream) {
@@ -579,10 +669,7 @@ extern "C" int PD_ENTRY(groupnorm_silu)(const float* x, const float* gamma, cons
   PD_CHECK_ARG(G <= 4096, "pd_groupnorm_silu: too many groups");
   const int nchunk = pd_groupnorm_nchunk(S, C);
   hipStream_t s = (hipStream_t)stream;
-  const int CV = C / 4, cpg = C / G;
-  const bool vec = (C % 4 == 0) && CV <= 256 && (256 % CV == 0) && (cpg % 4 == 0) && ld_out == C && G <= 256 &&
-                   (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && (((uintptr_t)out | (uintptr_t)out_lo) & 7) == 0 &&
-                   (!ss_scale || ((ld_ss % 4 == 0) && (((uintptr_t)ss_scale | (uintptr_t)ss_shift) & 15) == 0));
+  const bool vec = gn_vec_ok(C, G, x, gamma, beta, ss_scale, ss_shift, ld_ss) && ld_out == C && (((uintptr_t)out | (uintptr_t)out_lo) & 7) == 0;
   // bf16 engine (no lo half), 16-channel chunks holding whole groups, at most 26 x 128 rows: everything of a (sample, chunk) in registers
   if (vec && onepass && !out_lo && gn_onepass_fits(S, C, G)) {
     gn_onepass_launch(x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, nchunk, out, B, S, C, G, eps, silu,
@@ -590,14 +677,7 @@ extern "C" int PD_ENTRY(groupnorm_silu)(const float* x, const float* gamma, cons
     PD_CHECK_LAUNCH();
     return PD_OK;
   }
-  if (vec) {
-    hipLaunchKernelGGL(gn_stats_vec_kernel, dim3(nchunk, B), dim3(256), 0, s, x, partials, S, C, G);
-    PD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_apply_vec_kernel<false>, dim3(nchunk, B), dim3(256), 0, s, x, gamma, beta, ss_scale, ss_shift, ld_ss, partials,
-                       out, out_lo, S, C, G, eps, silu, nchunk, 1.f);
-    PD_CHECK_LAUNCH();
-    return PD_OK;
-  }
+  if (vec) return gn_two_pass<Out::Op16>(x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, out, out_lo, B, S, C, G, ld_out, eps, silu, 1.f, s);
   hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, B), dim3(256), (512 + 2 * G) * sizeof(double), s, x, partials, S, C, G);
   PD_CHECK_LAUNCH();
   hipLaunchKernelGGL(gn_apply_kernel, dim3(nchunk, B), dim3(256), 2 * G * sizeof(float), s, x, gamma, beta, ss_scale, ss_shift,
@@ -606,22 +686,17 @@ extern "C" int PD_ENTRY(groupnorm_silu)(const float* x, const float* gamma, cons
   return PD_OK;
 }
 
-// Statistics only: mean / rstd per (sample, group) as fp32 pairs, from the same fp64 partial sums and the same reduction order as the
-// apply kernels' prologue -- for consumers that normalise on the fly (pd_conv2d_gn_silu: the VAE's fused ResBlock convolution).
+// Statistics only: mean / rstd per (sample, group) as fp32 pairs from the same fp64 partial sums, the chunks summed serially: the order
+// of gn_apply_kernel's prologue (the vectorised apply kernel stripes the chunks, so its own mean / rstd may differ from these in the last
+// bit) -- for consumers that normalise on the fly (pd_conv2d_gn_silu: the VAE's fused ResBlock convolution).
 __global__ void __launch_bounds__(256) gn_finalize_kernel(const double* __restrict__ partials, float* __restrict__ stats, int S, int C, int G,
                                                           int nchunk, float eps) {
   const int b = blockIdx.x;
   const int cpg = C / G;
   for (int g = threadIdx.x; g < G; g += 256) {
-    double ss = 0, qq = 0;
-    const double* pp = partials + (int64_t)b * nchunk * G * 2 + g * 2;
-    for (int k = 0; k < nchunk; ++k) { ss += pp[(int64_t)k * G * 2]; qq += pp[(int64_t)k * G * 2 + 1]; }
-    const double cnt = (double)S * cpg;
-    const double mean = ss / cnt;
-    double var = qq / cnt - mean * mean;
-    if (var < 0) var = 0;
-    stats[((int64_t)b * G + g) * 2] = (float)mean;
-    stats[((int64_t)b * G + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    const float2 m = gn_stats_serial(partials + (int64_t)b * nchunk * G * 2, nchunk, G, g, (double)S * cpg, eps);
+    stats[((int64_t)b * G + g) * 2] = m.x;
+    stats[((int64_t)b * G + g) * 2 + 1] = m.y;
   }
 }
 
@@ -631,9 +706,7 @@ extern "C" int pd_groupnorm_stats(const float* x, double* partials, float* stats
   PD_CHECK_ARG(G > 0 && C % G == 0 && G <= 4096 && B > 0 && S > 0, "pd_groupnorm_stats: bad B/S/C/G (%d,%d,%d,%d)", B, S, C, G);
   const int nchunk = pd_groupnorm_nchunk(S, C);
   hipStream_t s = (hipStream_t)stream;
-  const int CV = C / 4, cpg = C / G;
-  const bool vec = (C % 4 == 0) && CV <= 256 && (256 % CV == 0) && (cpg % 4 == 0) && G <= 256 && (((uintptr_t)x) & 15) == 0;
-  if (vec) hipLaunchKernelGGL(gn_stats_vec_kernel, dim3(nchunk, B), dim3(256), 0, s, x, partials, S, C, G);
+  if (gn_vec_ok(C, G, x, nullptr, nullptr, nullptr, nullptr, 0)) hipLaunchKernelGGL(gn_stats_vec_kernel, dim3(nchunk, B), dim3(256), 0, s, x, partials, S, C, G);
   else hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, B), dim3(256), (512 + 2 * G) * sizeof(double), s, x, partials, S, C, G);
   PD_CHECK_LAUNCH();
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, partials, stats, S, C, G, nchunk, eps);
@@ -648,22 +721,28 @@ extern "C" int pd_groupnorm_silu_fp8(const float* x, const float* gamma, const f
   PD_CHECK_ARG(x && gamma && beta && partials && out, "pd_groupnorm_silu_fp8: null pointer");
   PD_CHECK_ARG(G > 0 && C % G == 0 && fp8_scale > 0.f, "pd_groupnorm_silu_fp8: bad C/G/scale (%d,%d,%g)", C, G, (double)fp8_scale);
   PD_CHECK_ARG((ss_scale == nullptr) == (ss_shift == nullptr), "pd_groupnorm_silu_fp8: scale/shift must come together");
-  const int nchunk = pd_groupnorm_nchunk(S, C);
-  const int CV = C / 4, cpg = C / G;
-  const bool vec = (C % 4 == 0) && CV <= 256 && (256 % CV == 0) && (cpg % 4 == 0) && G <= 256 &&
-                   (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && ((uintptr_t)out & 3) == 0 &&
-                   (!ss_scale || ((ld_ss % 4 == 0) && (((uintptr_t)ss_scale | (uintptr_t)ss_shift) & 15) == 0));
-  if (!vec) {
+  if (!(gn_vec_ok(C, G, x, gamma, beta, ss_scale, ss_shift, ld_ss) && ((uintptr_t)out & 3) == 0)) {
     pd_set_error("pd_groupnorm_silu_fp8: needs C %% 4 == 0, C/4 dividing 256 and 4 | C/G (C = %d, G = %d)", C, G);
     return PD_ERR_UNSUPPORTED;
   }
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(gn_stats_vec_kernel, dim3(nchunk, B), dim3(256), 0, s, x, partials, S, C, G);
-  PD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(gn_apply_vec_kernel<true>, dim3(nchunk, B), dim3(256), 0, s, x, gamma, beta, ss_scale, ss_shift, ld_ss, partials,
-                     (pd_bf16*)out, (pd_bf16*)nullptr, S, C, G, eps, silu, nchunk, fp8_scale);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
+  return gn_two_pass<Out::E4M3>(x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, out, nullptr, B, S, C, G, C, eps, silu, fp8_scale,
+                                (hipStream_t)stream);
+}
+
+// GroupNorm [-> scale-shift] [-> SiLU] -> MX e4m3 rows (the A operand of a pd_igemm_mx convolution); columns [C, ld_out) are padding
+extern "C" int pd_groupnorm_silu_mx(const float* x, const float* gamma, const float* beta, const float* ss_scale, const float* ss_shift,
+                                    int ld_ss, double* partials, uint8_t* out, uint8_t* scales, int B, int S, int C, int G, int ld_out,
+                                    float eps, int silu, pd_stream_t stream) {
+  PD_CHECK_ARG(x && gamma && beta && partials && out && scales, "pd_groupnorm_silu_mx: null pointer");
+  PD_CHECK_ARG(G > 0 && C % G == 0 && (C & 31) == 0, "pd_groupnorm_silu_mx: bad C/G (%d,%d): C must be a multiple of 32 (one scale per 32 channels)", C, G);
+  PD_CHECK_ARG(ld_out >= C && (ld_out & 31) == 0 && ld_out - C < 128, "pd_groupnorm_silu_mx: ld_out=%d must be a multiple of 32 in [C, C + 128)", ld_out);
+  PD_CHECK_ARG((ss_scale == nullptr) == (ss_shift == nullptr), "pd_groupnorm_silu_mx: scale/shift must come together");
+  if (!(gn_vec_ok(C, G, x, gamma, beta, ss_scale, ss_shift, ld_ss) && ((uintptr_t)out & 3) == 0)) {
+    pd_set_error("pd_groupnorm_silu_mx: needs C/4 dividing 256 and 4 | C/G (C = %d, G = %d)", C, G);
+    return PD_ERR_UNSUPPORTED;
+  }
+  return gn_two_pass<Out::MX>(x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, out, scales, B, S, C, G, ld_out, eps, silu, 0.f,
+                              (hipStream_t)stream);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -673,26 +752,6 @@ extern "C" int pd_groupnorm_silu_fp8(const float* x, const float* gamma, const f
 // Two passes like the forward: per-chunk fp64 partial sums of (dxh, dxh xh), then the apply pass reduces them in a fixed order
 // (deterministic).  mean / rstd are re-derived from the forward's partial sums.  A thread owns one channel; C divides 256.
 // -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void gn_reduce_partials(const double* __restrict__ pb, int nchunk, int G, double* spart, double* sout) {
-  // pb: this sample's (nchunk, G, 2) partial sums -> sout[2 g], sout[2 g + 1]; 256 / G threads per group stride the chunks
-  const int tid = threadIdx.x, LP = 256 / G;
-  if (tid < LP * G) {
-    const int g = tid % G, j = tid / G;
-    double a = 0, b = 0;
-    for (int k = j; k < nchunk; k += LP) { a += pb[((int64_t)k * G + g) * 2]; b += pb[((int64_t)k * G + g) * 2 + 1]; }
-    spart[tid * 2] = a;
-    spart[tid * 2 + 1] = b;
-  }
-  __syncthreads();
-  if (tid < G) {
-    double a = 0, b = 0;
-    for (int j = 0; j < LP; ++j) { a += spart[(j * G + tid) * 2]; b += spart[(j * G + tid) * 2 + 1]; }
-    sout[tid * 2] = a;
-    sout[tid * 2 + 1] = b;
-  }
-  __syncthreads();
-}
-
 template <bool APPLY>
 __global__ void __launch_bounds__(256) gn_silu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -705,13 +764,16 @@ __global__ void __launch_bounds__(256) gn_silu_bwd_kernel(const float* __restric
   const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
   const int cpg = C / G;
   const double cnt = (double)S * cpg;
-  gn_reduce_partials(fwd_partials + (int64_t)b * nchunk * G * 2, nchunk, G, spart, sfwd);
-  if (APPLY) gn_reduce_partials(bwd_partials + (int64_t)b * nchunk * G * 2, nchunk, G, spart, sbwd);
+  double t1, t2;
+  if (gn_reduce_partials(fwd_partials + (int64_t)b * nchunk * G * 2, nchunk, G, spart, t1, t2)) { sfwd[tid * 2] = t1; sfwd[tid * 2 + 1] = t2; }
+  __syncthreads();
+  if (APPLY) {
+    if (gn_reduce_partials(bwd_partials + (int64_t)b * nchunk * G * 2, nchunk, G, spart, t1, t2)) { sbwd[tid * 2] = t1; sbwd[tid * 2 + 1] = t2; }
+    __syncthreads();
+  }
   const int c = tid % C, rr = tid / C, RP = 256 / C, g = c / cpg;
-  const double mean_d = sfwd[g * 2] / cnt;
-  double var = sfwd[g * 2 + 1] / cnt - mean_d * mean_d;
-  if (var < 0) var = 0;
-  const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)eps));
+  const float2 mr = gn_mean_rstd(sfwd[g * 2], sfwd[g * 2 + 1], cnt, eps);
+  const float mean = mr.x, rstd = mr.y;
   const float ga = gamma[c], a = rstd * ga, d = beta[c] - mean * a;
   const float m1 = APPLY ? (float)(sbwd[g * 2] / cnt) : 0.f, m2 = APPLY ? (float)(sbwd[g * 2 + 1] / cnt) : 0.f;
   const int r0 = chunk * GN_ROWS, r1 = min(S, r0 + GN_ROWS);
@@ -789,13 +851,7 @@ __global__ void __launch_bounds__(256) cast_rows_kernel(const float* __restrict_
     const int64_t smp = ro / rows_out;
     const int r = (int)(ro - smp * rows_out);
     const float v = c < C ? x[(smp * rows_in + row_off + r) * (int64_t)ld_in + c] : 0.f;
-    if (out_lo) {
-      uint16_t hi, lo;
-      f2bf_split(v, hi, lo);
-      out[i] = hi; out_lo[i] = lo;
-    } else {
-      out[i] = f2op(v);
-    }
+    write1(out, out_lo, i, v);
   }
 }
 
@@ -816,172 +872,5 @@ extern "C" int PD_ENTRY(cast_rows)(const float* x, pd_bf16* out, pd_bf16* out_lo
   return PD_OK;
 }
 
-#if !PD_IS_F16
-// -------------------------------------------------------------------------------------------------
-// MX e4m3 outputs (the A operands of pd_igemm_mx): the two producers above with one E8M0 scale byte per 32 channels of a row beside
-// the payload.  Both own whole rows with four consecutive channels per lane, so a block is 8 consecutive lanes and its maximum three
-// shuffles: no extra pass over the tensor.  Separate kernels: the instantiations above stay as they are.
-// -------------------------------------------------------------------------------------------------
-// LayerNorm: one wave per row (the two-pass statistics of layernorm_kernel), NV float4 per lane
-template <int NV>
-__global__ void __launch_bounds__(256) layernorm_mx_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, uint8_t* __restrict__ out,
-                                                           uint8_t* __restrict__ scales, int64_t rows, int C, int ld_out, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  float4 v[NV];
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = j * 256 + lane * 4;
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < C) t = *(const float4*)(x + row * (int64_t)C + c);
-    v[j] = t;
-    s += (t.x + t.y) + (t.z + t.w);
-  }
-  const float mean = wave_sum(s) / (float)C;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = j * 256 + lane * 4;
-    if (c < C) {
-      const float a = v[j].x - mean, b = v[j].y - mean, cc = v[j].z - mean, d = v[j].w - mean;
-      q += (a * a + b * b) + (cc * cc + d * d);
-    }
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = j * 256 + lane * 4;
-    if (c >= ld_out) continue;                       // (ld_out % 32 == 0: the 8 lanes of a block leave together)
-    float y[4] = {0.f, 0.f, 0.f, 0.f};
-    if (c < C) {
-      const float4 g = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
-      y[0] = (v[j].x - mean) * rstd * g.x + be.x;
-      y[1] = (v[j].y - mean) * rstd * g.y + be.y;
-      y[2] = (v[j].z - mean) * rstd * g.z + be.z;
-      y[3] = (v[j].w - mean) * rstd * g.w + be.w;
-    }
-    int sb;
-    const uint32_t w = mx_quantize4(y, sb);
-    *(uint32_t*)(out + row * (int64_t)ld_out + c) = w;
-    if ((c & 31) == 0) scales[row * (int64_t)(ld_out >> 5) + (c >> 5)] = (uint8_t)sb;
-  }
-}
-
-extern "C" int pd_layernorm_mx(const float* x, const float* gamma, const float* beta, uint8_t* out, uint8_t* scales, int64_t rows, int C,
-                               int ld_out, float eps, pd_stream_t stream) {
-  PD_CHECK_ARG(x && gamma && beta && out && scales, "pd_layernorm_mx: null pointer");
-  PD_CHECK_ARG(C > 0 && (C & 31) == 0 && C <= 256 * LN_MAXV, "pd_layernorm_mx: C=%d must be a multiple of 32 (one scale per 32 channels) and <= %d", C,
-               256 * LN_MAXV);
-  PD_CHECK_ARG(ld_out >= C && (ld_out & 31) == 0 && ld_out <= ((C + 255) / 256) * 256,
-               "pd_layernorm_mx: ld_out=%d must be >= C, a multiple of 32 and within the last 256-column block", ld_out);
-  PD_CHECK_ARG((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && ((uintptr_t)out & 3) == 0, "pd_layernorm_mx: misaligned pointer");
-  if (rows <= 0) return PD_OK;
-  const int nv = (C + 255) / 256;
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  hipStream_t s = (hipStream_t)stream;
-#define PD_LNMX(NV) hipLaunchKernelGGL((layernorm_mx_kernel<NV>), grid, dim3(256), 0, s, x, gamma, beta, out, scales, rows, C, ld_out, eps)
-  if (nv <= 1) PD_LNMX(1);
-  else if (nv <= 2) PD_LNMX(2);
-  else if (nv <= 4) PD_LNMX(4);
-  else if (nv <= 8) PD_LNMX(8);
-  else PD_LNMX(16);
-#undef PD_LNMX
-  PD_CHECK_LAUNCH();
-  return PD_OK;
-}
-
-// GroupNorm [-> scale-shift] [-> SiLU]: the apply pass of gn_apply_vec_kernel (same statistics prologue, same arithmetic) with an MX output
-__global__ void __launch_bounds__(256) gn_apply_mx_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, const float* __restrict__ ss_scale,
-                                                          const float* __restrict__ ss_shift, int ld_ss,
-                                                          const double* __restrict__ partials, uint8_t* __restrict__ out,
-                                                          uint8_t* __restrict__ scales, int S, int C, int G, int ld_out, float eps, int silu,
-                                                          int nchunk) {
-  __shared__ float smr[2 * 256];
-  __shared__ double spart[2 * 256];
-  const int b = blockIdx.y, chunk = blockIdx.x;
-  const int cpg = C / G;
-  const int tid = threadIdx.x;
-  const int LP = 256 / G;
-  if (tid < LP * G) {
-    const int g = tid % G, j = tid / G;
-    double ss = 0, qq = 0;
-    const double* pp = partials + (int64_t)b * nchunk * G * 2 + g * 2;
-    for (int k = j; k < nchunk; k += LP) { ss += pp[(int64_t)k * G * 2]; qq += pp[(int64_t)k * G * 2 + 1]; }
-    spart[tid * 2] = ss;
-    spart[tid * 2 + 1] = qq;
-  }
-  __syncthreads();
-  if (tid < G) {
-    double ss = 0, qq = 0;
-    for (int j = 0; j < LP; ++j) { ss += spart[(j * G + tid) * 2]; qq += spart[(j * G + tid) * 2 + 1]; }
-    const double cnt = (double)S * cpg, mean = ss / cnt;
-    double var = qq / cnt - mean * mean;
-    if (var < 0) var = 0;
-    smr[tid * 2] = (float)mean;
-    smr[tid * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
-  __syncthreads();
-  const int CV = C >> 2, RP = 256 / CV;
-  const int cv = tid % CV, rr = tid / CV, c = cv * 4, g = c / cpg;
-  const float mean = smr[g * 2], rstd = smr[g * 2 + 1];
-  float4 ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
-  float a[4] = {rstd * ga.x, rstd * ga.y, rstd * ga.z, rstd * ga.w};
-  float d[4] = {be.x - mean * a[0], be.y - mean * a[1], be.z - mean * a[2], be.w - mean * a[3]};
-  if (ss_scale) {
-    const float4 sc = *(const float4*)(ss_scale + (int64_t)b * ld_ss + c), sh = *(const float4*)(ss_shift + (int64_t)b * ld_ss + c);
-    const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { a[k] *= (1.f + scv[k]); d[k] = d[k] * (1.f + scv[k]) + shv[k]; }
-  }
-  const int r0 = chunk * GN_ROWS, r1 = min(S, r0 + GN_ROWS);
-  const int lds = ld_out >> 5, padv = (ld_out - C) >> 2;
-  for (int r = rr; r < r1 - r0; r += RP) {           // (the 8 lanes of a block share r: C % 32 == 0)
-    const int64_t row = (int64_t)b * S + r0 + r;
-    const float4 v = *(const float4*)(x + row * C + c);
-    float y[4] = {v.x * a[0] + d[0], v.y * a[1] + d[1], v.z * a[2] + d[2], v.w * a[3] + d[3]};
-    if (silu) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) y[k] = y[k] / (1.f + expf(-y[k]));      // (expf, not __expf: a rounding boundary of the payload is 2^-4 away)
-    }
-    int sb;
-    const uint32_t w = mx_quantize4(y, sb);
-    *(uint32_t*)(out + row * ld_out + c) = w;
-    if ((c & 31) == 0) scales[row * lds + (c >> 5)] = (uint8_t)sb;
-    for (int pc = cv; pc < padv; pc += CV) {         // pad columns [C, ld_out): zero payload, scale byte 0
-      *(uint32_t*)(out + row * ld_out + C + pc * 4) = 0u;
-      if ((pc & 7) == 0) scales[row * lds + ((C + pc * 4) >> 5)] = 0;
-    }
-  }
-}
-
-extern "C" int pd_groupnorm_silu_mx(const float* x, const float* gamma, const float* beta, const float* ss_scale, const float* ss_shift,
-                                    int ld_ss, double* partials, uint8_t* out, uint8_t* scales, int B, int S, int C, int G, int ld_out,
-                                    float eps, int silu, pd_stream_t stream) {
-  PD_CHECK_ARG(x && gamma && beta && partials && out && scales, "pd_groupnorm_silu_mx: null pointer");
-  PD_CHECK_ARG(G > 0 && C % G == 0 && (C & 31) == 0, "pd_groupnorm_silu_mx: bad C/G (%d,%d): C must be a multiple of 32 (one scale per 32 channels)", C, G);
-  PD_CHECK_ARG(ld_out >= C && (ld_out & 31) == 0 && ld_out - C < 128, "pd_groupnorm_silu_mx: ld_out=%d must be a multiple of 32 in [C, C + 128)", ld_out);
-  PD_CHECK_ARG((ss_scale == nullptr) == (ss_shift == nullptr), "pd_groupnorm_silu_mx: scale/shift must come together");
-  const int nchunk = pd_groupnorm_nchunk(S, C);
-  const int CV = C / 4, cpg = C / G;
-  const bool vec = CV <= 256 && (256 % CV == 0) && (cpg % 4 == 0) && G <= 256 &&
-                   (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && ((uintptr_t)out & 3) == 0 &&
-                   (!ss_scale || ((ld_ss % 4 == 0) && (((uintptr_t)ss_scale | (uintptr_t)ss_shift) & 15) == 0));
-  if (!vec) {
-    pd_set_error("pd_groupnorm_silu_mx: needs C/4 dividing 256 and 4 | C/G (C = %d, G = %d)", C, G);
-    return PD_ERR_UNSUPPORTED;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(gn_stats_vec_kernel, dim3(nchunk, B), dim3(256), 0, s, x, partials, S, C, G);
-  PD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(gn_apply_mx_kernel, dim3(nchunk, B), dim3(256), 0, s, x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, out, scales,
-                     S, C, G, ld_out, eps, silu, nchunk);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
-}
-#endif
 
 }  // namespace PD_NS

@@ -577,22 +577,22 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         def resblock(name, m: TimeEmbedResBlock):
             norm(name + ".gn1", m.in_layers[0]); conv(name + ".conv1", m.in_layers[2])
             norm(name + ".gn2", m.out_layers[0]); conv(name + ".conv2", m.out_layers[3])
+            def gn_vec_ok(Cc, G):
+                # the shape conditions of the library's vectorised GroupNorm (gn_vec_ok in csrc/norm.hip), mirrored so that a layer
+                # pd_groupnorm_silu_fp8 / _mx would refuse keeps 16-bit operands instead of raising at forward time
+                return Cc % 4 == 0 and (Cc // 4) <= 256 and 256 % (Cc // 4) == 0 and Cc % G == 0 and (Cc // G) % 4 == 0 and G <= 256
+
             if self.fp8_conv:
-                # the library's conditions, mirrored so that a layer it would refuse keeps bf16 operands instead of raising at forward time:
-                # pd_groupnorm_silu_fp8 (vector path: (C/G) % 4 == 0, G <= 256, C/4 | 256) and pd_igemm fp8 (256-tile kernel: C % 128 == 0)
+                # ... and pd_igemm fp8 (256-tile kernel: C % 128 == 0)
                 for cn, cm, G in ((".conv1", m.in_layers[2], m.in_groups), (".conv2", m.out_layers[3], m.out_groups)):
-                    Cc = cm.in_channels
-                    if (Cc % 128 == 0 and (Cc // 4) <= 256 and 256 % (Cc // 4) == 0 and Cc % G == 0 and (Cc // G) % 4 == 0 and G <= 256
-                            and cm.out_channels % 64 == 0):
+                    if cm.in_channels % 128 == 0 and gn_vec_ok(cm.in_channels, G) and cm.out_channels % 64 == 0:
                         P[name + cn + ".w8"] = pack_conv_fp8(cm.weight.to(device))      # (e4m3 (27, N, C), scale)
                         gnm = m.in_layers[0] if cn == ".conv1" else m.out_layers[0]
                         P[name + cn + ".a8s"] = self._fp8_act_scale(gnm.weight, gnm.bias, cn == ".conv2" and m.use_embed and m.use_scale_shift_norm)
             if self.mx_conv:
-                # the library's conditions, mirrored as above: pd_groupnorm_silu_mx (C % 32 == 0, C/4 | 256, 4 | C/G, G <= 256)
+                # ... and one scale per 32 channels (C % 32 == 0)
                 for cn, cm, G in ((".conv1", m.in_layers[2], m.in_groups), (".conv2", m.out_layers[3], m.out_groups)):
-                    Cc = cm.in_channels
-                    if (Cc % 32 == 0 and (Cc // 4) <= 256 and 256 % (Cc // 4) == 0 and Cc % G == 0 and (Cc // G) % 4 == 0 and G <= 256
-                            and tuple(cm.weight.shape[2:]) == (3, 3, 3)):
+                    if cm.in_channels % 32 == 0 and gn_vec_ok(cm.in_channels, G) and tuple(cm.weight.shape[2:]) == (3, 3, 3):
                         P[name + cn + ".wmx"] = pack_conv_mx(cm.weight.to(device), name + cn)     # (e4m3 (27, N, pad128(C)), E8M0 scales)
             if m.use_embed:
                 P[name + ".emb.w"], P[name + ".emb.b"] = f32(m.emb_layers[1].weight), f32(m.emb_layers[1].bias)
@@ -733,20 +733,17 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         """GroupNorm `gn` [-> scale-shift] -> SiLU as the A operand of convolution `conv`: e4m3 rows (value * the layer's activation scale)
         where the layer has an e4m3 weight record (precision="fp8" / "fp8_conv"), else 16-bit rows."""
         g, beta = P[gn + ".g"], P[gn + ".beta"]
+        if (conv + ".wmx") not in P and (conv + ".w8") not in P:
+            return self._groupnorm(x, g, beta, B, S, C, G, "gn.a", dev, 1e-5, ss=ss, opts=self._opts_for(B))
+        part, kw = self._gn_args(B, S, C, G, dev, ss)
         if (conv + ".wmx") in P:
             ld = pad128(C)
             q = self._buf("gn.a.mx", (B * S, ld), torch.float8_e4m3fn, dev)
             sc = self._buf("gn.a.mxs", (B * S, ld // 32), torch.uint8, dev)
-            part = self._buf("gn.part", (B * L.groupnorm_nchunk(S, C) * G * 2,), torch.float64, dev)
-            kw = dict(ss_scale=ss, ss_shift=ss[:, C:], ld_ss=2 * C) if ss is not None else {}
             L.groupnorm_silu_mx(x, g, beta, part, q, sc, B, S, C, G, 1e-5, silu=True, **kw)
             return Act(q, None, ld, None, sc)
-        if (conv + ".w8") not in P:
-            return self._groupnorm(x, g, beta, B, S, C, G, "gn.a", dev, 1e-5, ss=ss, opts=self._opts_for(B))
         scale = P[conv + ".a8s"]
         a8 = self._buf("gn.a.f8", (B * S, C), torch.float8_e4m3fn, dev)
-        part = self._buf("gn.part", (B * L.groupnorm_nchunk(S, C) * G * 2,), torch.float64, dev)
-        kw = dict(ss_scale=ss, ss_shift=ss[:, C:], ld_ss=2 * C) if ss is not None else {}
         L.groupnorm_silu_fp8(x, g, beta, part, a8, B, S, C, G, 1e-5, scale, silu=True, **kw)
         return Act(a8, None, C, scale)
 

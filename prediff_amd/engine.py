@@ -76,12 +76,17 @@ class HipEngine:
         L.cast_rows(x, *a, samples, rows if rows_in is None else rows_in, row_off, rows, C, C, ld, opts=self.opts)
         return Act(*a, ld)
 
+    def _gn_args(self, B, S, C, G, dev, ss=None):
+        """What every GroupNorm launch takes beside its output: the fp64 partial-sum workspace and the scale-shift keywords of `ss`
+        ((B, 2 C) fp32 rows, scale then shift; None: no scale-shift)."""
+        part = self._buf("gn.part", (B * L.groupnorm_nchunk(S, C) * G * 2,), torch.float64, dev)
+        return part, (dict(ss_scale=ss, ss_shift=ss[:, C:], ld_ss=2 * C) if ss is not None else {})
+
     def _groupnorm(self, x, g, beta, B, S, C, G, name, dev, eps, silu=True, ss=None, opts=None) -> Act:
         """GroupNorm [-> scale-shift `ss`] [-> SiLU] of channels-last fp32 x (B, S, C) -> 16-bit operand rows."""
         ld = pad64(C)
         a = self._bf(name, B * S, ld, dev)
-        part = self._buf("gn.part", (B * L.groupnorm_nchunk(S, C) * G * 2,), torch.float64, dev)
-        kw = dict(ss_scale=ss, ss_shift=ss[:, C:], ld_ss=2 * C) if ss is not None else {}
+        part, kw = self._gn_args(B, S, C, G, dev, ss)
         L.groupnorm_silu(x, g, beta, part, *a, B, S, C, G, ld, eps, silu=silu, **kw, opts=opts or self.opts)
         return Act(*a, ld)
 
