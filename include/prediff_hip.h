@@ -444,6 +444,26 @@ int pd_ffn_rows_supported(int C, int hidden, int act);
 int pd_ffn_rows(const float* x, float* out, const void* wffn, const float* vecs, int64_t rows, int units, float eps,
                 const pd_call_opts* opts, pd_stream_t stream);
 
+/* The SEVIR pixel front end (DESIGN.md §7 "SEVIR pixel front end"; prediff_amd/sevir_io.py): raw VIL events to model frames and back.
+ * pd_sevir_ingest: raw (N, H, W, T) uint8, layout NHWT (public SEVIR VIL: (N, 384, 384, 49)), to fp32 NTHWC frames with C = 1, one launch:
+ *   LR frame t' = raw frame t' ft (T_lr = ceil(T / ft) of them); LR cell (h', w') = the maximum of the BYTES of the raw block
+ *   [h' fh, h' fh + fh) x [w' fw, w' fw + fw) (save_downsampled_dataset, datasets/sevir/sevir_dataloader.py:460-467: block_reduce with
+ *   np.max); value = scale * ((float)byte + offset), ONE fp32 add then ONE fp32 multiply, never an fma (preprocess_data_dict, :645;
+ *   scale and offset arrive rounded to fp32 once).  H % fh == 0 and W % fw == 0.
+ *   starts: nwin int32 LR frame indices ON THE DEVICE (the library cannot read the table: the caller checks 0 <= start <= T_lr - in_len -
+ *   out_len; a window outside that range reads nothing and is written as zeros).  Sequence n * nwin + k is window k of event n:
+ *   ctx (N nwin, in_len, H / fh, W / fw, 1) = LR frames [start_k, start_k + in_len), tgt (N nwin, out_len, H / fh, W / fw, 1) the out_len
+ *   frames after them; tgt is NULL exactly when out_len = 0.  Every element of ctx and tgt is written exactly once; raw is only read, and
+ *   nothing outside it is read whatever its alignment.  No synchronisation and no host reads: the launch can be captured.
+ * pd_sevir_export: x (B, T, H, W, 1) fp32 to the VIL scale, v = x / scale - offset: ONE correctly rounded fp32 divide by the fp32 scale,
+ *   then ONE fp32 subtract (process_data_dict_back, :679).  mode PD_SEVIR_F32: out is fp32 (B, T, H, W, 1) = v.  PD_SEVIR_U8_NTHW /
+ *   PD_SEVIR_U8_NHWT: out is uint8 (B, T, H, W) / (B, H, W, T) = v clamped to [0, 255] and rounded half to even (torch.round); a NaN
+ *   becomes 0.  out must not alias x.  Any alignment (16-byte accesses when both buffers allow them). */
+enum pd_sevir_export_mode { PD_SEVIR_F32 = 0, PD_SEVIR_U8_NTHW = 1, PD_SEVIR_U8_NHWT = 2 };
+int pd_sevir_ingest(const uint8_t* raw, const int32_t* starts, float* ctx, float* tgt, int N, int H, int W, int T, int ft, int fh, int fw,
+                    int nwin, int in_len, int out_len, float scale, float offset, pd_stream_t stream);
+int pd_sevir_export(const float* x, void* out, int64_t B, int T, int H, int W, float scale, float offset, int mode, pd_stream_t stream);
+
 /* SEVIRSkillScore.update (datasets/sevir/evaluation.py:193-239): hits / misses / false alarms of (pred / divisor) vs
  * (target / divisor) at every threshold (>=, NaN in either input counts nowhere), accumulated into counts[thr][t][3]
  * (int64, keep_seq) or counts[thr][3].  Tensors are (outer, T, inner) fp32 in [0,1]; divisor = fp32(1/255). */

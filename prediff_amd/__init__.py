@@ -13,5 +13,6 @@ from .cuboid_transformer_unet import CuboidTransformerUNet  # noqa: E402,F401
 from .latent_diffusion import LatentDiffusion  # noqa: E402,F401
 from .tiled import TileGeometry, TiledLatentDiffusion  # noqa: E402,F401
 from .rollout import RolloutPlan, rollout_ensemble, rollout_sample  # noqa: E402,F401
+from .sevir_io import SEVIRFrontEnd  # noqa: E402,F401
 from .i3d import InceptionI3d  # noqa: E402,F401
 from .fvd import FrechetVideoDistance  # noqa: E402,F401

@@ -153,6 +153,8 @@ _PROTOS = {
     "pd_window_gather": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
     "pd_window_blend": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),
     "pd_context_advance": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.c_float] + [C.c_int] * 3 + [C.c_void_p]),
+    "pd_sevir_ingest": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float] * 2 + [C.c_void_p]),
+    "pd_sevir_export": (C.c_int, [C.c_void_p] * 2 + [C.c_int64] + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_int, C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -676,6 +678,30 @@ def context_advance(ctx, z, origins, ctx_next, stride, z_scale, forecast=None, f
     _check(lib().pd_context_advance(ptr(ctx), ptr(z), ptr(table), ptr(ctx_next), ptr(forecast) if f_cnt else None, B, nwin, T_in, T_out,
                                     Hc, Wc, h, w, Cn, stride, float(z_scale), f_T, f_off, f_cnt, stream_ptr()),
            "pd_context_advance")
+
+
+def sevir_ingest(raw, starts, ctx, tgt, N, H, W, T, factors, nwin, in_len, out_len, scale, offset):
+    """pd_sevir_ingest: raw (N, H, W, T) uint8 -> ctx (N nwin, in_len, H / fh, W / fw, 1) and tgt (..., out_len, ...) fp32 (tgt None with
+    out_len = 0); starts: nwin int32 LR frame indices on the device, checked by the caller.  scale / offset are rounded to fp32 here."""
+    ft, fh, fw = factors
+    _dev(raw, torch.uint8), _dev(starts, torch.int32), _dev(ctx, torch.float32)
+    if tgt is not None:
+        _dev(tgt, torch.float32)
+    Hl, Wl = H // fh, W // fw
+    if (raw.numel() != N * H * W * T or starts.numel() != nwin or ctx.numel() != N * nwin * in_len * Hl * Wl
+            or (tgt.numel() if tgt is not None else 0) != N * nwin * out_len * Hl * Wl):
+        raise PrediffHipError(f"sevir_ingest: raw {tuple(raw.shape)} / {starts.numel()} starts / ctx {tuple(ctx.shape)} / tgt "
+                              f"{None if tgt is None else tuple(tgt.shape)} do not hold {N} x {nwin} windows of {in_len} + {out_len} frames of {Hl} x {Wl}")
+    _check(lib().pd_sevir_ingest(ptr(raw), ptr(starts), ptr(ctx), ptr(tgt), N, H, W, T, ft, fh, fw, nwin, in_len, out_len, float(scale),
+                                 float(offset), stream_ptr()), "pd_sevir_ingest")
+
+
+def sevir_export(x, out, B, T, H, W, scale, offset, mode):
+    """pd_sevir_export: x (B, T, H, W, 1) fp32 -> x / scale - offset as fp32 (mode 0) or as clamped, rounded bytes NTHW (1) / NHWT (2)."""
+    _dev(x, torch.float32), _dev(out, torch.float32 if mode == 0 else torch.uint8)
+    if x.numel() != B * T * H * W or out.numel() != x.numel() or out.device != x.device:
+        raise PrediffHipError(f"sevir_export: x {tuple(x.shape)} / out {tuple(out.shape)} do not hold ({B}, {T}, {H}, {W}) on one device")
+    _check(lib().pd_sevir_export(ptr(x), ptr(out), B, T, H, W, float(scale), float(offset), mode, stream_ptr()), "pd_sevir_export")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):
