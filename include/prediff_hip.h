@@ -99,7 +99,8 @@ typedef struct pd_igemm_args {
   int32_t debug_flags;     /* profiling ablations only: 1 skip main loop, 2 skip stores, 4 skip activation, 8 keep the dense tap loop of the 256 x 256 Conv3d kernels (tile 11 skips nothing: no effect),
                               16 the automatic choice keeps the tap-streamed 256 x 256 kernel where it would take a halo-staged one (tile 10 or 11), 64 four-phase K-tile (0 in production),
                               128 (tests of pd_igemm_mx, which alone reads it; pd_igemm ignores it) K-split into two to four slices whenever a workspace is given, whatever the
-                              grid: the split form at shapes too short (fewer than 32 K-tiles) to split by themselves */
+                              grid: the split form at shapes too short (fewer than 32 K-tiles) to split by themselves,
+                              256 the halo-staged Conv3d kernels (tile 10 or 11) keep the MFMAs of the row tiles that read only the zero ring (the dense schedule; identical bits) */
   int32_t ksplit;          /* set by the library: K-slices of a split-K launch (1 = none) */
   float* splitk_ws;        /* caller workspace for split-K partial sums (fp32, splitk_ws_elems elements) or NULL: without it a launch
                               is never split.  Used for small grids (few trajectories per launch): the K loop of a long-K launch is cut

@@ -32,6 +32,21 @@
 // A kt whose input frame lies outside the sample is left out as a whole group (A and W): the tile-wide tap skipping of igemm256_kernel;
 // debug_flags bit 8 keeps the dense loop (zero halos streamed, identical bits).
 //
+// Border-row skip (conv3d_halo_kernel<L, true>, the default; debug_flags bit 256 launches <L, false>, the dense MFMA schedule, for A/B runs
+// and as the tests' reference).  A row tile is one image row, so the row tile of image row 0 reads, for the three taps with kh = 0, halo row
+// 0 and nothing else: sixteen cells of the zero ring, whatever kw.  Likewise image row 15 and halo row 17 at kh = 2.  Those row tiles are
+// left out of their phase -- both k-steps against all four column tiles, 8 of the phase's 32 MFMAs, and the two LDS reads of the A fragment:
+//   wave row 0: local row tile 0 in phase A of K-tiles j = 0, 1, 2 (kh = j / 3 is a compile-time value in the unrolled loop);
+//   wave row 1: local row tile 7 (local tile 3 of phase B) in phase B of K-tiles j = 6, 7, 8.
+// 24 of a wave's 576 MFMAs per group (4.17 %).  The two wave rows leave out different tiles, so the loop is compiled once per wave row and
+// entered through one scalar branch on the (wave-uniform) wave row: no test inside the loop, the code of the kernel grows by the two extra
+// copies of the nine-K-tile body (112.6 -> 128.9 KB, most of either being the epilogue).  Every barrier, DMA piece and vmcnt constant is in
+// both copies exactly where it was: no VMEM instruction is added or removed per wave, so the hazard analysis above holds unchanged; in a
+// shortened section six accumulators (not eight) lie between two MFMAs on the same one.
+// Exactness: a product left out is 0 * w.  An accumulator starts at +0 and can never become -0 ((+0) + (+-0) = +0 in round-to-nearest), so
+// for finite weights adding +-0 changes no bit: the stored output is bit-identical to the dense schedule's.  With an Inf or NaN WEIGHT the
+// dense schedule makes 0 * w = NaN in those border rows and this one does not -- the property the whole-group temporal skip above already has.
+//
 // Level 1 (conv3d_halo_kernel<1>, tile 11): 8 x 8 frames.  A 256-row tile is FOUR frame slots (frames 4 tm .. 4 tm + 3 of the batch; T need
 // not be a multiple of 4, so a tile may hold the last frames of one sample and the first of the next), and a group's halo is the four input
 // frames of its kt.  Everything above holds with these differences:
@@ -48,6 +63,9 @@
 //    staging lane carries its cell's slot and tests it against the group's four-bit validity mask; slots past the last frame (B * T not a
 //    multiple of 4) are never valid, and the epilogue stores no row >= M.
 //  - No group is skipped (all four slots are out of range only when T = 1): debug_flags bit 8 changes nothing.
+//  - Border-row skip: row tile i is image row i of BOTH frame slots of the wave row, so row tile 0 at kh = 0 (halo row 0 of both slots) and
+//    row tile 7 at kh = 2 (halo row 9) are all-zero in both wave rows: a compile-time condition, one copy of the loop, 48 of a wave's 576
+//    MFMAs per group (8.33 %).  (A slot whose temporal tap is out of range is zero as a whole, but only for that slot and that tile.)
 #include <algorithm>
 #include "common.h"
 #include "igemm_epilogue.h"
@@ -104,7 +122,7 @@ struct FragH {
 };
 }  // namespace
 
-template <int L>
+template <int L, bool BORDER>
 __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int PLROWS = Lay<L>::ROWS, PLANE = Lay<L>::PLANE, HALO = Lay<L>::HALO, NEXTRA = Lay<L>::NEXTRA, PITCH = Lay<L>::PITCH,
@@ -261,18 +279,23 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
   (f).v[0] = *(const op8*)((base) + ((lg ^ swz) * 16)); (f).v[1] = *(const op8*)((base) + (((4 + lg) ^ swz) * 16))
 #define LOAD_A(f, base) \
   (f).v[0] = *(const op8*)(base); (f).v[1] = *(const op8*)((base) + 4 * PLANE)
-  // one quadrant: 4 row tiles x 2 column tiles x K = 64 (two k-steps); consecutive MFMAs hit different accumulators
-#define QUAD16(R0, C0, bfrag)                                                                               \
+  // one quadrant: 4 row tiles x 2 column tiles x K = 64 (two k-steps); consecutive MFMAs hit different accumulators.  SK = local row tile
+  // left out (-1: none): a[SK] is then neither loaded nor read, and six accumulators still lie between two MFMAs on the same one
+#define QUAD16(R0, C0, bfrag, SK)                                                                           \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                          \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                           \
-      _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                         \
-        acc[(R0) + i][(C0) + c] = mfma_16x16x32(a[i].v[ks], bfrag[c].v[ks], acc[(R0) + i][(C0) + c]);
+      if (i != (SK))                                                                                        \
+        _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                       \
+          acc[(R0) + i][(C0) + c] = mfma_16x16x32(a[i].v[ks], bfrag[c].v[ks], acc[(R0) + i][(C0) + c]);
 
   int wcur = 0;
   // one group of nine K-tiles; has_next (another group follows: its halo and the W tiles of its first two K-tiles are issued here) is a
   // compile-time flag -- the last group is a second copy of the body, and the steady-state loop carries no test for it
-  auto group = [&](auto has_next_t, int g) {
+  // WR: the wave row the copy is compiled for (border-row skip at level 0, where the all-zero row tiles differ between the wave rows: -1 = none)
+  auto group = [&](auto has_next_t, auto wr_t, int g) {
     constexpr bool has_next = decltype(has_next_t)::value;
+    constexpr int WR = decltype(wr_t)::value;
+    constexpr bool skip_top = BORDER && (L == 1 || WR == 0), skip_bot = BORDER && (L == 1 || WR == 1);
     const int hnxt = (g & 1) ^ 1;
     const char* sA = smem + (g & 1) * HALO + a_rd;
     if (has_next) next_halo();
@@ -280,11 +303,13 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
     for (int j = 0; j < 9; ++j) {
       const int shift = ((j / 3) * PITCH + (j % 3)) * 16;    // byte offset of tap (kh, kw) inside a plane
       const char* sB = smem + wcur * WBUF + b_rd;
+      const int skA = j < 3 && skip_top ? 0 : -1, skB = j >= 6 && skip_bot ? 3 : -1;   // local row tile left out: kh = j / 3, all compile-time
       // ---------- phase A: all four W column tiles, A row tiles 0-3; quadrants (A0, W0), (A0, W1); a halo piece of group g + 1 ----------
 #pragma unroll
       for (int c = 0; c < 2; ++c) { LOAD_B(b0[c], sB + c * (16 * 128)); }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) { LOAD_A(a[i], sA + shift + i * (PITCH * 16)); }
+      for (int i = 0; i < 4; ++i)
+        if (i != skA) { LOAD_A(a[i], sA + shift + i * (PITCH * 16)); }
 #pragma unroll
       for (int c = 0; c < 2; ++c) { LOAD_B(b1[c], sB + (2 + c) * (16 * 128)); }
       if (j >= 1 && j <= 5 && has_next) {
@@ -293,13 +318,14 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
       }
       PHASE_SYNC();
       __builtin_amdgcn_s_setprio(1);
-      QUAD16(0, 0, b0)
-      QUAD16(0, 2, b1)
+      QUAD16(0, 0, b0, skA)
+      QUAD16(0, 2, b1, skA)
       __builtin_amdgcn_s_setprio(0);
       PHASE_SYNC();
       // ---------- phase B: A row tiles 4-7; quadrants (A1, W1), (A1, W0); W of K-tile k + 2; wait for K-tile k + 1 ----------
 #pragma unroll
-      for (int i = 0; i < 4; ++i) { LOAD_A(a[i], sA + shift + (4 + i) * (PITCH * 16)); }
+      for (int i = 0; i < 4; ++i)
+        if (i != skB) { LOAD_A(a[i], sA + shift + (4 + i) * (PITCH * 16)); }
       if (j <= 6 || has_next) {
         if (j == 7) next_w_group();
         issue_w(wcur);
@@ -313,15 +339,23 @@ __global__ void __launch_bounds__(512) conv3d_halo_kernel(const pd_igemm_args p)
       }
       PHASE_SYNC();
       __builtin_amdgcn_s_setprio(1);
-      QUAD16(4, 2, b1)
-      QUAD16(4, 0, b0)
+      QUAD16(4, 2, b1, skB)
+      QUAD16(4, 0, b0, skB)
       __builtin_amdgcn_s_setprio(0);
       PHASE_SYNC();
       wcur ^= 1;
     }
   };
-  for (int g = 0; g + 1 < ngroups; ++g) group(std::true_type{}, g);
-  if (ngroups > 0) group(std::false_type{}, ngroups - 1);
+  auto groups = [&](auto wr_t) {
+    for (int g = 0; g + 1 < ngroups; ++g) group(std::true_type{}, wr_t, g);
+    if (ngroups > 0) group(std::false_type{}, wr_t, ngroups - 1);
+  };
+  if constexpr (L == 0 && BORDER) {            // one copy of the loop per wave row (wr is wave-uniform: a scalar branch, taken once)
+    if (wr == 0) groups(std::integral_constant<int, 0>{});
+    else groups(std::integral_constant<int, 1>{});
+  } else {
+    groups(std::integral_constant<int, -1>{});
+  }
 #undef QUAD16
 #undef LOAD_A
 #undef LOAD_B
@@ -366,13 +400,13 @@ bool pd_conv3d_halo_supported(const pd_igemm_args& a, int kind, int level) {
   return a.Hi == fw && a.Wi == fw && a.Ho == fw && a.Wo == fw && a.Ti == a.To;
 }
 
-template <int L>
+template <int L, bool BORDER>
 static int launch_halo(const pd_igemm_args& a, hipStream_t s) {
   constexpr int LDS = Lay<L>::LDS;
   static bool attr_set_dev[PD_MAX_DEVICES];
   bool& attr_set = attr_set_dev[pd_cur_device()];
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3d_halo_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    hipError_t e = hipFuncSetAttribute((const void*)conv3d_halo_kernel<L, BORDER>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     if (e != hipSuccess) {
       pd_set_error("pd_igemm: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
       return PD_ERR_LAUNCH;
@@ -380,11 +414,14 @@ static int launch_halo(const pd_igemm_args& a, hipStream_t s) {
     attr_set = true;
   }
   const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
-  hipLaunchKernelGGL(conv3d_halo_kernel<L>, dim3(tiles, 1, 1), dim3(512), LDS, s, a);
+  hipLaunchKernelGGL((conv3d_halo_kernel<L, BORDER>), dim3(tiles, 1, 1), dim3(512), LDS, s, a);
   PD_CHECK_LAUNCH();
   return PD_OK;
 }
 
-int pd_conv3d_halo_launch(const pd_igemm_args& a, int level, hipStream_t s) { return level ? launch_halo<1>(a, s) : launch_halo<0>(a, s); }
+int pd_conv3d_halo_launch(const pd_igemm_args& a, int level, hipStream_t s) {
+  if (a.debug_flags & 256) return level ? launch_halo<1, false>(a, s) : launch_halo<0, false>(a, s);   // (A/B: the dense MFMA schedule)
+  return level ? launch_halo<1, true>(a, s) : launch_halo<0, true>(a, s);
+}
 
 }  // namespace PD_NS
