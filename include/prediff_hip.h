@@ -506,6 +506,22 @@ int pd_frame_score_update(const float* pred, const float* target, int M, const i
                           const int64_t* target_strides, float data_range, float* range_buf, int keep_seq, double* sums,
                           long long* counts, double* ws, int64_t ws_doubles, pd_stream_t stream);
 
+/* Radially averaged power spectra of forecast / observation pairs (the RAPSD diagnostic of the nowcasting literature, with the spectral
+ * coherence): pred holds M members of target's shape (1 <= M <= 512), both fp32, read in place; every (member, n, t, c) plane of pred is
+ * paired with the (n, t, c) plane of target.  With P, T the 2-D DFTs of the two H x W frames of a pair (after the window: 0 none,
+ * 1 periodic Hann) and s = 1 / (H W), per radial bin b and step t (t = 0 unless keep_seq), in fp64 and in a fixed order
+ * (bit-reproducible): sums[0][t][b] += s |P|^2, sums[1][t][b] += s |T|^2, sums[2][t][b] += s Re(P conj T) over the cells of the bin;
+ * frames[t] += pairs (int64).  No NaN masking.  The bins are the caller's: cell_order (device int32, the kept cells ky W + kx sorted by
+ * bin) and bin_start (device int32[nb + 1]), nb = max(H, W) / 2 + 1 (prediff_amd/spectrum.py: spectrum_bins).
+ * sizes: host int64[5] = N, T, H, W, C; H and W are 2^a or 3 * 2^a, 8 .. 512 (else PD_ERR_ARG, the message names the side).
+ * pred_strides: host int64[6] = member, N, T, H, W, C element strides; target_strides: host int64[5].  ws: device workspace, 8-byte
+ * aligned; pd_spectrum_ws_bytes(M, sizes) is what holds every pair of the call, capped at 256 MiB (-1: unsupported shape, host-only);
+ * a smaller workspace (at least pd_spectrum_ws_bytes(1, {1, 1, H, W, 1})) makes the call run in several chunks of pairs. */
+int64_t pd_spectrum_ws_bytes(int M, const int64_t* sizes);
+int pd_spectrum_update(const float* pred, const float* target, int M, const int64_t* sizes, const int64_t* pred_strides,
+                       const int64_t* target_strides, const int* cell_order, const int* bin_start, int nb, int window, int keep_seq,
+                       double* sums, long long* frames, void* ws, int64_t ws_bytes, pd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Fréchet video distance (evaluation/fvd/): the pieces of the I3D feature engine that are not pd_igemm, and the feature moments.
  * ------------------------------------------------------------------------------------------------- */

@@ -177,6 +177,9 @@ _PROTOS = {
     "pd_frame_score_ws_doubles": (C.c_int64, [C.c_int, C.c_void_p]),
     "pd_frame_score_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_int]
                               + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "pd_spectrum_ws_bytes": (C.c_int64, [C.c_int, C.c_void_p]),
+    "pd_spectrum_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 3
+                           + [C.c_int64, C.c_void_p]),
     "pd_i3d_preprocess": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_maxpool3d_same": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_i3d_head": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
@@ -750,6 +753,19 @@ def frame_score_update(pred, target, M, sizes, pred_strides, target_strides, dat
     _check(lib().pd_frame_score_update(ptr(pred), ptr(target), int(M), _i64(sizes), _i64(pred_strides), _i64(target_strides),
                                        float(data_range), ptr(range_buf), 1 if keep_seq else 0, ptr(sums), ptr(counts), ptr(ws),
                                        ws.numel(), stream_ptr()), "pd_frame_score_update")
+
+
+def spectrum_ws_bytes(M, sizes):
+    return int(lib().pd_spectrum_ws_bytes(int(M), _i64(sizes)))
+
+
+def spectrum_update(pred, target, M, sizes, pred_strides, target_strides, cell_order, bin_start, nb, window, keep_seq, sums, frames, ws):
+    """pred_strides: member stride followed by the (N, T, H, W, C) strides; cell_order / bin_start: int32 device tensors of
+    spectrum.spectrum_bins; window: 0 none, 1 periodic Hann; sums fp64 [3, T', nb], frames int64 [T']; ws: uint8 workspace (a workspace
+    below spectrum_ws_bytes(M, sizes) makes the call run in several chunks of pairs)."""
+    _check(lib().pd_spectrum_update(ptr(pred), ptr(target), int(M), _i64(sizes), _i64(pred_strides), _i64(target_strides),
+                                    ptr(cell_order), ptr(bin_start), int(nb), int(window), 1 if keep_seq else 0, ptr(sums), ptr(frames),
+                                    ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "pd_spectrum_update")
 
 
 I3D_RES, I3D_STEM_WO, I3D_STEM_LD = 224, 112, 64          # pd_i3d_preprocess: crop side, operand rows per image row, operand row length
