@@ -465,6 +465,24 @@ int pd_sevir_ingest(const uint8_t* raw, const int32_t* starts, float* ctx, float
                     int nwin, int in_len, int out_len, float scale, float offset, pd_stream_t stream);
 int pd_sevir_export(const float* x, void* out, int64_t B, int T, int H, int W, float scale, float offset, int mode, pd_stream_t stream);
 
+/* Optical-flow extrapolation (Lagrangian persistence; not in the reference; DESIGN.md §7 "Extrapolation baseline"; the definition is the
+ * module docstring of prediff_amd/extrapolation.py).  fp32, fixed summation order: the same input gives the same bits.  No synchronisation
+ * and no host reads: both calls can be captured.
+ * pd_lk_motion: ctx (B, T, H, W, 1) fp32 -> motion (B, 2, H, W) fp32 = (v_y, v_x) in pixels per frame: pyramidal (levels), iterated (iters
+ *   per level), damped Lucas-Kanade flow over the P = min(pairs, T - 1) newest frame pairs, window (2 radius + 1)^2.  T >= 2; H, W <= 512,
+ *   divisible by 2^(levels - 1), the coarsest sides >= 4; 1 <= levels <= 8, 1 <= iters <= 64, 1 <= radius <= 9, P <= 16, damping > 0.
+ *   ws: device workspace (4-byte aligned) of pd_lk_ws_bytes(...) bytes (-1: unsupported shape or options; host-only): the pyramid above
+ *   level 0 and two flow buffers per level.  levels - 1 + levels * iters launches.
+ * pd_advect: out (B, K, H, W, 1)[k - 1] = the frame sampled bilinearly at (y - k v_y, x - k v_x), k = 1 .. K, one launch.  frame: B images
+ *   of H x W, frame_stride elements apart (>= H W: the last frame of a context is read in place); motion (B, 2, H, W), any values: a tap
+ *   outside the frame reads `fill`, a coordinate that is not finite or further than 2^20 from the frame gives `fill`.  out aliases
+ *   neither input. */
+int64_t pd_lk_ws_bytes(int64_t B, int T, int H, int W, int levels, int iters, int radius, int pairs);
+int pd_lk_motion(const float* ctx, float* motion, int64_t B, int T, int H, int W, int levels, int iters, int radius, float damping, int pairs,
+                 void* ws, int64_t ws_bytes, pd_stream_t stream);
+int pd_advect(const float* frame, const float* motion, float* out, int64_t B, int K, int H, int W, int64_t frame_stride, float fill,
+              pd_stream_t stream);
+
 /* SEVIRSkillScore.update (datasets/sevir/evaluation.py:193-239): hits / misses / false alarms of (pred / divisor) vs
  * (target / divisor) at every threshold (>=, NaN in either input counts nowhere), accumulated into counts[thr][t][3]
  * (int64, keep_seq) or counts[thr][3].  Tensors are (outer, T, inner) fp32 in [0,1]; divisor = fp32(1/255). */

@@ -17,3 +17,4 @@ from .sevir_io import SEVIRFrontEnd  # noqa: E402,F401
 from .i3d import InceptionI3d  # noqa: E402,F401
 from .fvd import FrechetVideoDistance  # noqa: E402,F401
 from .spectrum import SEVIRSpectralScore  # noqa: E402,F401
+from .extrapolation import LagrangianPersistence  # noqa: E402,F401

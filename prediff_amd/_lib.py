@@ -155,6 +155,9 @@ _PROTOS = {
     "pd_context_advance": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.c_float] + [C.c_int] * 3 + [C.c_void_p]),
     "pd_sevir_ingest": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float] * 2 + [C.c_void_p]),
     "pd_sevir_export": (C.c_int, [C.c_void_p] * 2 + [C.c_int64] + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_int, C.c_void_p]),
+    "pd_lk_ws_bytes": (C.c_int64, [C.c_int64] + [C.c_int] * 7),
+    "pd_lk_motion": (C.c_int, [C.c_void_p] * 2 + [C.c_int64] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pd_advect": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 3 + [C.c_int64, C.c_float, C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -705,6 +708,31 @@ def sevir_export(x, out, B, T, H, W, scale, offset, mode):
     if x.numel() != B * T * H * W or out.numel() != x.numel() or out.device != x.device:
         raise PrediffHipError(f"sevir_export: x {tuple(x.shape)} / out {tuple(out.shape)} do not hold ({B}, {T}, {H}, {W}) on one device")
     _check(lib().pd_sevir_export(ptr(x), ptr(out), B, T, H, W, float(scale), float(offset), mode, stream_ptr()), "pd_sevir_export")
+
+
+def lk_ws_bytes(B, T, H, W, levels, iters, radius, pairs):
+    """pd_lk_ws_bytes: the workspace of lk_motion at this shape, -1 for an unsupported shape or option (host-only)."""
+    return int(lib().pd_lk_ws_bytes(int(B), int(T), int(H), int(W), int(levels), int(iters), int(radius), int(pairs)))
+
+
+def lk_motion(ctx, motion, B, T, H, W, levels, iters, radius, damping, pairs, ws):
+    """pd_lk_motion: ctx (B, T, H, W, 1) fp32 -> motion (B, 2, H, W) fp32 = (v_y, v_x); ws: a device tensor of lk_ws_bytes(...) bytes."""
+    _dev(ctx, torch.float32), _dev(motion, torch.float32), _dev(ws)
+    if ctx.numel() != B * T * H * W or motion.numel() != B * 2 * H * W or motion.device != ctx.device or ws.device != ctx.device:
+        raise PrediffHipError(f"lk_motion: ctx {tuple(ctx.shape)} / motion {tuple(motion.shape)} do not hold ({B}, {T}, {H}, {W}) on one device")
+    _check(lib().pd_lk_motion(ptr(ctx), ptr(motion), B, T, H, W, int(levels), int(iters), int(radius), float(damping), int(pairs), ptr(ws),
+                              ws.numel() * ws.element_size(), stream_ptr()), "pd_lk_motion")
+
+
+def advect(frame, motion, out, B, K, H, W, frame_stride, fill):
+    """pd_advect: frame (B images of H x W fp32, `frame_stride` elements apart, each contiguous) and motion (B, 2, H, W) -> out
+    (B, K, H, W, 1), lead k at [:, k - 1]."""
+    _dev(motion, torch.float32), _dev(out, torch.float32)
+    if not frame.is_cuda or frame.dtype != torch.float32:
+        raise PrediffHipError(f"advect: the frame must be a float32 CUDA(HIP) tensor, got {frame.dtype} on {frame.device}")
+    if motion.numel() != B * 2 * H * W or out.numel() != B * K * H * W or motion.device != frame.device or out.device != frame.device:
+        raise PrediffHipError(f"advect: motion {tuple(motion.shape)} / out {tuple(out.shape)} do not hold ({B}, {K}, {H}, {W}) on one device")
+    _check(lib().pd_advect(ptr(frame), ptr(motion), ptr(out), B, K, H, W, int(frame_stride), float(fill), stream_ptr()), "pd_advect")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):

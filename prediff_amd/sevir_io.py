@@ -14,6 +14,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from ._args import as_int as _int
 
 # (scale, offset) of preprocess_data_dict per rescale mode and data type (the reference's PREPROCESS_SCALE_* / PREPROCESS_OFFSET_*
 # tables, sevir_dataloader.py:25-44): Python floats, rounded to fp32 once where they meet the fp32 tensor
@@ -25,16 +26,6 @@ DATA_TYPES = ("vis", "ir069", "ir107", "vil", "lght")
 EXPORT_MODE = {(torch.float32, "NTHWC"): 0, (torch.uint8, "NTHW"): 1, (torch.uint8, "NHWT"): 2}      # enum pd_sevir_export_mode
 
 _start_tables = {}       # (starts, device) -> the device copy
-
-
-def _int(name, v):
-    try:
-        ok = not isinstance(v, bool) and int(v) == v
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{name} must be an integer, got {v!r}")
-    return int(v)
 
 
 def _start_table(starts: Tuple[int, ...], device):
