@@ -483,6 +483,31 @@ int pd_lk_motion(const float* ctx, float* motion, int64_t B, int T, int H, int W
 int pd_advect(const float* frame, const float* motion, float* out, int64_t B, int K, int H, int W, int64_t frame_stride, float fill,
               pd_stream_t stream);
 
+/* Stochastic extrapolation (STEPS; S-PROG without noise; not in the reference; DESIGN.md §7 "Stochastic extrapolation"; the definition is
+ * the module docstring of prediff_amd/steps.py, whose step numbers are used here).  fp32 fields, fp64 statistics in a fixed order, no
+ * atomics: the same input gives the same bits.  No synchronisation and no host reads: every call can be captured.
+ * Frames: H and W are 2^a or 3 * 2^a, >= 8, H W <= 16384 (one complex frame stays in LDS); 2 <= levels <= floor(log2(max(H, W))) - 1;
+ * ar_order 1 or 2; ctx (B, T, H, W, 1) with T >= ar_order + 1; motion (B, 2, H, W); bands (levels, H, W): real, even weights
+ * (prediff_amd.steps.steps_bands).  ws: device workspace, 8-byte aligned.
+ * pd_steps_ws_bytes: what the workspace of B sequences and M members holds (-1: unsupported; host-only).  M = 0 is what pd_steps_analyse
+ *   alone needs; pd_steps_evolve needs the size of its own M and the workspace pd_steps_analyse filled.
+ * pd_steps_analyse (steps 0 .. 5, one workgroup per sequence): mu, sigma (B, levels) of the cascade of the last frame (a dead level
+ *   reports sigma 0), phi (B, levels, 3) = (phi1, phi2, phi0), gamma (B, levels, 2); the normalised levels of the two newest Lagrangian
+ *   frames and the noise filter P go to the workspace.
+ * pd_steps_evolve (steps 6 .. 8, one workgroup per (member, sequence), looping over the leads): noise (M, B, K, H, W) standard
+ *   normal, or NULL for zero innovations -> R (M, B, K, H, W), the recomposed Lagrangian fields.  mu / sigma / phi: what pd_steps_analyse
+ *   wrote.  Two cascade levels of ONE member travel as one complex frame (an odd `levels` leaves the last pair half empty); members are
+ *   never packed with each other, so a member alone, with its own noise, gives the bits it gives inside any ensemble.  R aliases no input.
+ * pd_steps_finish (step 9, one workgroup per (member, sequence, lead)): mask (0 none, 1 "obs"), match (0 none, 1 "mean"), the threshold
+ *   cut and pd_advect's rule at the single lead k with fill 0: R (M, B, K, H, W) -> out (M, B, K, H, W, 1).  out aliases no input. */
+int64_t pd_steps_ws_bytes(int64_t B, int M, int H, int W, int levels, int ar_order);
+int pd_steps_analyse(const float* ctx, const float* motion, const float* bands, int64_t B, int T, int H, int W, int levels, int ar_order,
+                     float threshold, float* mu, float* sigma, float* phi, float* gamma, void* ws, int64_t ws_bytes, pd_stream_t stream);
+int pd_steps_evolve(const float* noise, const float* bands, const float* mu, const float* sigma, const float* phi, int M, int64_t B, int K,
+                    int H, int W, int levels, int ar_order, float* R, void* ws, int64_t ws_bytes, pd_stream_t stream);
+int pd_steps_finish(const float* ctx, const float* motion, const float* R, float* out, int M, int64_t B, int T, int K, int H, int W,
+                    float threshold, int mask, int match, pd_stream_t stream);
+
 /* SEVIRSkillScore.update (datasets/sevir/evaluation.py:193-239): hits / misses / false alarms of (pred / divisor) vs
  * (target / divisor) at every threshold (>=, NaN in either input counts nowhere), accumulated into counts[thr][t][3]
  * (int64, keep_seq) or counts[thr][3].  Tensors are (outer, T, inner) fp32 in [0,1]; divisor = fp32(1/255). */

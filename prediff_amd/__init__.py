@@ -18,3 +18,4 @@ from .i3d import InceptionI3d  # noqa: E402,F401
 from .fvd import FrechetVideoDistance  # noqa: E402,F401
 from .spectrum import SEVIRSpectralScore  # noqa: E402,F401
 from .extrapolation import LagrangianPersistence  # noqa: E402,F401
+from .steps import StochasticExtrapolation, steps_bands  # noqa: E402,F401

@@ -158,6 +158,10 @@ _PROTOS = {
     "pd_lk_ws_bytes": (C.c_int64, [C.c_int64] + [C.c_int] * 7),
     "pd_lk_motion": (C.c_int, [C.c_void_p] * 2 + [C.c_int64] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "pd_advect": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 3 + [C.c_int64, C.c_float, C.c_void_p]),
+    "pd_steps_ws_bytes": (C.c_int64, [C.c_int64] + [C.c_int] * 5),
+    "pd_steps_analyse": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 5 + [C.c_float] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+    "pd_steps_evolve": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int64, C.c_void_p]),
+    "pd_steps_finish": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int64] + [C.c_int] * 4 + [C.c_float] + [C.c_int] * 2 + [C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -733,6 +737,50 @@ def advect(frame, motion, out, B, K, H, W, frame_stride, fill):
     if motion.numel() != B * 2 * H * W or out.numel() != B * K * H * W or motion.device != frame.device or out.device != frame.device:
         raise PrediffHipError(f"advect: motion {tuple(motion.shape)} / out {tuple(out.shape)} do not hold ({B}, {K}, {H}, {W}) on one device")
     _check(lib().pd_advect(ptr(frame), ptr(motion), ptr(out), B, K, H, W, int(frame_stride), float(fill), stream_ptr()), "pd_advect")
+
+
+def steps_ws_bytes(B, M, H, W, levels, ar_order):
+    """pd_steps_ws_bytes: the workspace of B sequences and M members (M = 0: what steps_analyse alone needs), -1 for an unsupported
+    shape or option (host-only)."""
+    return int(lib().pd_steps_ws_bytes(int(B), int(M), int(H), int(W), int(levels), int(ar_order)))
+
+
+def _steps_operands(fn, device, operands):
+    for name, x, need in operands:
+        if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.device != device or x.numel() != need:
+            raise PrediffHipError(f"{fn}: {name} must be a contiguous fp32 tensor of {need} elements on {device}, got {tuple(x.shape)} "
+                                  f"{x.dtype} on {x.device}")
+
+
+def steps_analyse(ctx, motion, bands, B, T, H, W, levels, ar_order, threshold, mu, sigma, phi, gamma, ws):
+    """pd_steps_analyse: ctx (B, T, H, W, 1), motion (B, 2, H, W), bands (levels, H, W) -> mu, sigma (B, levels), phi (B, levels, 3),
+    gamma (B, levels, 2); ws: a device tensor of at least steps_ws_bytes(B, 0, ...) bytes, which pd_steps_evolve reads."""
+    _dev(ws)
+    _steps_operands("steps_analyse", ctx.device, (("ctx", ctx, B * T * H * W), ("motion", motion, B * 2 * H * W), ("bands", bands, levels * H * W),
+                                                  ("mu", mu, B * levels), ("sigma", sigma, B * levels), ("phi", phi, B * levels * 3),
+                                                  ("gamma", gamma, B * levels * 2)))
+    _check(lib().pd_steps_analyse(ptr(ctx), ptr(motion), ptr(bands), B, T, H, W, int(levels), int(ar_order), float(threshold), ptr(mu), ptr(sigma),
+                                  ptr(phi), ptr(gamma), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "pd_steps_analyse")
+
+
+def steps_evolve(noise, bands, mu, sigma, phi, M, B, K, H, W, levels, ar_order, R, ws):
+    """pd_steps_evolve: noise (M, B, K, H, W) or None -> R (M, B, K, H, W); mu / sigma / phi and ws as pd_steps_analyse left them, ws of
+    at least steps_ws_bytes(B, M, ...) bytes."""
+    _dev(ws)
+    _steps_operands("steps_evolve", R.device, (() if noise is None else (("noise", noise, M * B * K * H * W),)) + (
+        ("bands", bands, levels * H * W), ("mu", mu, B * levels), ("sigma", sigma, B * levels), ("phi", phi, B * levels * 3),
+        ("R", R, M * B * K * H * W)))
+    _check(lib().pd_steps_evolve(ptr(noise), ptr(bands), ptr(mu), ptr(sigma), ptr(phi), int(M), B, K, H, W, int(levels), int(ar_order), ptr(R),
+                                 ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "pd_steps_evolve")
+
+
+def steps_finish(ctx, motion, R, out, M, B, T, K, H, W, threshold, mask, match):
+    """pd_steps_finish: R (M, B, K, H, W) -> out (M, B, K, H, W, 1): mask (0 / 1 "obs"), match (0 / 1 "mean"), the threshold cut and the
+    advection of lead k."""
+    _steps_operands("steps_finish", ctx.device, (("ctx", ctx, B * T * H * W), ("motion", motion, B * 2 * H * W), ("R", R, M * B * K * H * W),
+                                                 ("out", out, M * B * K * H * W)))
+    _check(lib().pd_steps_finish(ptr(ctx), ptr(motion), ptr(R), ptr(out), int(M), B, T, K, H, W, float(threshold), int(mask), int(match),
+                                 stream_ptr()), "pd_steps_finish")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):
