@@ -508,6 +508,27 @@ int pd_steps_evolve(const float* noise, const float* bands, const float* mu, con
 int pd_steps_finish(const float* ctx, const float* motion, const float* R, float* out, int M, int64_t B, int T, int K, int H, int W,
                     float threshold, int mask, int match, pd_stream_t stream);
 
+/* Growth / decay extrapolation (ANVIL, deterministic; not in the reference; DESIGN.md §7 "Growth and decay extrapolation"; the definition
+ * is the module docstring of prediff_amd/anvil.py, whose step numbers are used here).  An ARI(p, 1) model of the cascade levels in
+ * Lagrangian coordinates whose AR parameters are estimated per pixel in a Gaussian window.  fp32 fields, the one fp64 sum in a fixed
+ * order, no atomics: the same input gives the same bits.  No synchronisation and no host reads: every call can be captured.
+ * Frames, levels and bands as pd_steps_*; ar_order p is 1 or 2; ctx (B, T, H, W, 1) with T >= p + 2; motion (B, 2, H, W).
+ * window: the 2 radius + 1 fp32 weights g[-radius .. radius] of step 6 on the device, 1 <= radius <= 96; window_sum_sq: W0 of step 7,
+ * (sum_d g[d])^2, which the host knows.  ws: device workspace, 16-byte aligned; phi, gamma and R are 16-byte aligned too.
+ * pd_anvil_ws_bytes: what the workspace of B sequences holds (-1: unsupported; host-only).
+ * pd_anvil_analyse (steps 2 .. 8): one launch of B x 2 workgroups for the forward spectra of the packed Lagrangian frames (and mean(A_0^2)),
+ *   one of B x levels workgroups for the levels, their differences, the windowed moments and the per-pixel Yule-Walker solve:
+ *   phi (B, levels, 2, H, W) = (phi1, phi2), gamma (B, levels, 2, H, W) = the clamped (gamma_1, gamma_2); Y_l0 and D_l0 .. D_lp stay in
+ *   the workspace.
+ * pd_anvil_evolve (step 9, pointwise): phi and the workspace pd_anvil_analyse filled -> R (B, K, H, W), the recomposed Lagrangian
+ *   fields, lead k at [:, k - 1].  R aliases no input.  Step 10 is pd_steps_finish with M = 1, mask = 0, match = 0. */
+int64_t pd_anvil_ws_bytes(int64_t B, int H, int W, int levels, int ar_order);
+int pd_anvil_analyse(const float* ctx, const float* motion, const float* bands, const float* window, int radius, double window_sum_sq,
+                     int64_t B, int T, int H, int W, int levels, int ar_order, float* phi, float* gamma, void* ws, int64_t ws_bytes,
+                     pd_stream_t stream);
+int pd_anvil_evolve(const float* phi, int64_t B, int K, int H, int W, int levels, int ar_order, float* R, const void* ws, int64_t ws_bytes,
+                    pd_stream_t stream);
+
 /* SEVIRSkillScore.update (datasets/sevir/evaluation.py:193-239): hits / misses / false alarms of (pred / divisor) vs
  * (target / divisor) at every threshold (>=, NaN in either input counts nowhere), accumulated into counts[thr][t][3]
  * (int64, keep_seq) or counts[thr][3].  Tensors are (outer, T, inner) fp32 in [0,1]; divisor = fp32(1/255). */

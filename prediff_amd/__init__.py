@@ -19,3 +19,4 @@ from .fvd import FrechetVideoDistance  # noqa: E402,F401
 from .spectrum import SEVIRSpectralScore  # noqa: E402,F401
 from .extrapolation import LagrangianPersistence  # noqa: E402,F401
 from .steps import StochasticExtrapolation, steps_bands  # noqa: E402,F401
+from .anvil import AutoregressiveExtrapolation  # noqa: E402,F401

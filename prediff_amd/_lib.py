@@ -162,6 +162,9 @@ _PROTOS = {
     "pd_steps_analyse": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 5 + [C.c_float] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
     "pd_steps_evolve": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int64, C.c_void_p]),
     "pd_steps_finish": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int64] + [C.c_int] * 4 + [C.c_float] + [C.c_int] * 2 + [C.c_void_p]),
+    "pd_anvil_ws_bytes": (C.c_int64, [C.c_int64] + [C.c_int] * 4),
+    "pd_anvil_analyse": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_double, C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "pd_anvil_evolve": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int64, C.c_void_p]),
     "pd_nchw_to_nhwc": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_nhwc_to_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "pd_ffn_fused_supported": (C.c_int, [C.c_int, C.c_int]),
@@ -781,6 +784,38 @@ def steps_finish(ctx, motion, R, out, M, B, T, K, H, W, threshold, mask, match):
                                                  ("out", out, M * B * K * H * W)))
     _check(lib().pd_steps_finish(ptr(ctx), ptr(motion), ptr(R), ptr(out), int(M), B, T, K, H, W, float(threshold), int(mask), int(match),
                                  stream_ptr()), "pd_steps_finish")
+
+
+def anvil_ws_bytes(B, H, W, levels, ar_order):
+    """pd_anvil_ws_bytes: the workspace of B sequences, -1 for an unsupported shape or option (host-only)."""
+    return int(lib().pd_anvil_ws_bytes(int(B), int(H), int(W), int(levels), int(ar_order)))
+
+
+def anvil_analyse(ctx, motion, bands, window, window_sum_sq, B, T, H, W, levels, ar_order, phi, gamma, ws):
+    """pd_anvil_analyse: ctx (B, T, H, W, 1), motion (B, 2, H, W), bands (levels, H, W), window (2 r + 1,) = g[-r .. r] with
+    window_sum_sq = (sum g)^2 -> phi, gamma (B, levels, 2, H, W); ws: a device tensor of at least anvil_ws_bytes(...) bytes, which
+    pd_anvil_evolve reads."""
+    _dev(ws)
+    if window.dim() != 1 or window.numel() < 3 or window.numel() % 2 == 0:
+        raise PrediffHipError(f"anvil_analyse: window must hold the 2 r + 1 weights g[-r .. r], r >= 1, got {tuple(window.shape)}")
+    _steps_operands("anvil_analyse", ctx.device, (("ctx", ctx, B * T * H * W), ("motion", motion, B * 2 * H * W), ("bands", bands, levels * H * W),
+                                                  ("window", window, window.numel()), ("phi", phi, B * levels * 2 * H * W),
+                                                  ("gamma", gamma, B * levels * 2 * H * W)))
+    if ws.device != ctx.device:
+        raise PrediffHipError(f"anvil_analyse: ctx is on {ctx.device}, the workspace on {ws.device}")
+    _check(lib().pd_anvil_analyse(ptr(ctx), ptr(motion), ptr(bands), ptr(window), window.numel() // 2, float(window_sum_sq), B, T, H, W,
+                                  int(levels), int(ar_order), ptr(phi), ptr(gamma), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
+           "pd_anvil_analyse")
+
+
+def anvil_evolve(phi, B, K, H, W, levels, ar_order, R, ws):
+    """pd_anvil_evolve: phi (B, levels, 2, H, W) and ws as pd_anvil_analyse left them -> R (B, K, H, W)."""
+    _dev(ws)
+    _steps_operands("anvil_evolve", R.device, (("phi", phi, B * levels * 2 * H * W), ("R", R, B * K * H * W)))
+    if ws.device != R.device:
+        raise PrediffHipError(f"anvil_evolve: R is on {R.device}, the workspace on {ws.device}")
+    _check(lib().pd_anvil_evolve(ptr(phi), B, K, H, W, int(levels), int(ar_order), ptr(R), ptr(ws), ws.numel() * ws.element_size(),
+                                 stream_ptr()), "pd_anvil_evolve")
 
 
 def nchw_to_nhwc(x, out, N, Cn, HW, ld_out):
