@@ -121,7 +121,11 @@ typedef struct pd_igemm_args {
                               the activations rounded once) -- `taps` = 2 f, W holds the f taps of W_hi followed by the f taps of W_lo, and the
                               K loop walks the activation gather of tap (t mod f) against weight slab t: D = A W_hi^T + A W_lo^T in one fp32
                               accumulator.  f = KT * KH * KW (1 for a row-wise linear layer).  0: one product (taps = KT * KH * KW) */
-  int32_t reserved0;
+  int32_t rowtab_rows;     /* rows of `rowtab` (> 0 with a table; was reserved0) */
+  const float* rowtab;     /* (appended; pd_sizeof_igemm_args grows by 8)  fp32 [rowtab_rows][N] or NULL: out row m += rowtab[m % rowtab_rows], added LAST -- after alpha, bias,
+                              row vector, activation, gate and residual, i.e. ((acc + bias) + residual) + table: the bits of a
+                              pd_add_rowtable launch behind this one (the positional table behind first_proj's second convolution).
+                              fp32 output only, never together with a split-K workspace */
 } pd_igemm_args;
 int pd_igemm(const pd_igemm_args* a, pd_stream_t stream);
 
@@ -283,6 +287,12 @@ int pd_softmax_rows(const float* x, pd_bf16* out, pd_bf16* out_lo, int64_t rows,
 int pd_unet_build_input(const float* x, const float* cond, float* out, int B, int T_in, int T_out, int HW, int C,
                         int ld_out, pd_stream_t stream);
 
+/* pd_unet_build_input that also writes the bfloat16 copy of its rows (out16: rows of ld16 elements, zero padded: what pd_cast_rows
+ * makes of `out`), in the same pass: the A operand of the stem's skip convolution.  C a multiple of 4, ld16 a multiple of 4 in
+ * (C, 2 C]; x / cond 16 B aligned.  bfloat16 only. */
+int pd_unet_build_input16(const float* x, const float* cond, float* out, pd_bf16* out16, int B, int T_in, int T_out, int HW,
+                          int C, int ld_out, int ld16, pd_stream_t stream);
+
 /* Sinusoidal timestep embedding [cos(t f_k) | sin(t f_k)] (models/utils.py:68-88), t int64 (B,) -> fp32 (B, dim).
  * freqs: dim/2 fp32 frequencies exp(-ln(max_period) k / half), computed once on the host exactly as the reference does. */
 int pd_timestep_embedding(const int64_t* t, const float* freqs, float* out, int B, int dim, pd_stream_t stream);
@@ -291,6 +301,20 @@ int pd_timestep_embedding(const int64_t* t, const float* freqs, float* out, int 
  * emb_layers :105-113).  W (N, K) row-major fp32. */
 int pd_linear_small(const float* x, const float* W, const float* b, float* out, int M, int K, int N, int act_in,
                     int act_out, pd_stream_t stream);
+
+/* The whole timestep-embedding chain of the denoiser (pd_timestep_embedding -> pd_linear_small (SiLU out) -> pd_linear_small -> one
+ * SiLU-in pd_linear_small per TimeEmbedResBlock) in four launches: sinusoid, first layer, second layer, all `nproj` projections.
+ * Every buffer the chain writes is written (sin_out (B, dim), h1 (B, E), temb (B, E), proj_out[q] (B, proj_N[q])), bit-equal to the
+ * chain's: per output the summation order is pd_linear_small's.  A wave keeps one weight row in registers for all B rows and the
+ * activation rows are staged in LDS once per eight columns, so a weight is read once per launch, not once per row.  (One launch would need a device-wide wait between the layers -- each output of
+ * a layer reads every output of the one before -- which this library does not do.)  dim: a multiple of 4 up to 256; E: one up to
+ * 1024 (pd_time_embed_supported); W0 (E, dim), W2 (E, E), proj_W[q] (proj_N[q], E) row-major fp32, 16 B aligned; the bias pointers
+ * may be NULL.  proj_* are HOST arrays of nproj <= PD_TIME_EMBED_MAX_PROJ entries. */
+#define PD_TIME_EMBED_MAX_PROJ 8
+int pd_time_embed_supported(int dim, int E);
+int pd_time_embed(const int64_t* t, const float* freqs, const float* W0, const float* b0, const float* W2, const float* b2,
+                  const float* const* proj_W, const float* const* proj_b, float* const* proj_out, const int* proj_N, int nproj,
+                  float* sin_out, float* h1, float* temb, int B, int dim, int E, pd_stream_t stream);
 
 /* x[b, s, c] += table[s, c] (PosEmbed with the three tables pre-summed; cuboid_transformer.py:65-90) */
 int pd_add_rowtable(float* x, const float* table, int64_t n_samples, int rows_per_sample, int C, pd_stream_t stream);

@@ -38,7 +38,7 @@ class IgemmArgs(C.Structure):
                [("alpha", C.c_float), ("tile", C.c_int32), ("vec_epilogue", C.c_int32), ("a_bytes", C.c_uint32), ("w_bytes", C.c_uint32), ("debug_flags", C.c_int32), ("ksplit", C.c_int32),
                 ("splitk_ws", C.c_void_p), ("splitk_ws_elems", C.c_int64), ("fp8", C.c_int32), ("out_fp8_log2", C.c_int32),
                 ("operand", C.c_int32), ("disable_256", C.c_int32), ("min_k_256", C.c_int32), ("splitk_max_tiles", C.c_int32),
-                ("w_fold", C.c_int32), ("reserved0", C.c_int32)]
+                ("w_fold", C.c_int32), ("rowtab_rows", C.c_int32), ("rowtab", C.c_void_p)]
 
 
 class CuboidAttnArgs(C.Structure):
@@ -55,6 +55,7 @@ class MxOperands(C.Structure):
                 ("ld_w_scales", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
 
 
+TIME_EMBED_MAX_PROJ = 8                     # PD_TIME_EMBED_MAX_PROJ
 OPERAND = {"bf16": 0, "fp16": 1}            # enum pd_operand
 
 
@@ -139,8 +140,11 @@ _PROTOS = {
     "pd_cuboid_attention_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 9 + [C.c_float, C.c_void_p]),
     "pd_softmax_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 3 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_unet_build_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]),
+    "pd_unet_build_input16": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
     "pd_timestep_embedding": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p]),
     "pd_linear_small": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
+    "pd_time_embed_supported": (C.c_int, [C.c_int, C.c_int]),
+    "pd_time_embed": (C.c_int, [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "pd_add_rowtable": (C.c_int, [C.c_void_p] * 2 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "pd_add": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "pd_ddpm_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
@@ -260,7 +264,8 @@ def igemm(A, W, *, M, N, Cin, lda=None, ldw=None, taps=1, w_tap_stride=0, geom=N
           A_lo=None, W_lo=None, bias=None, rowvec=None, rows_per_sample=0, residual=None, res_period=0,
           ld_res=None, mul=None, act="none", alpha=1.0, out_f32=None, out_bf16=None, out_bf16_lo=None,
           ld_out=None, ld_outb=None, nbatch=1, a_batch_stride=0, w_batch_stride=0, out_batch_stride=0,
-          outb_batch_stride=0, res_batch_stride=0, tile=0, debug_flags=0, splitk_ws=None, fp8=False, out_fp8_log2=0, opts=None):
+          outb_batch_stride=0, res_batch_stride=0, tile=0, debug_flags=0, splitk_ws=None, fp8=False, out_fp8_log2=0, rowtab=None,
+          opts=None):
     """Thin wrapper around pd_igemm.  `geom` = dict(B,Ti,Hi,Wi,To,Ho,Wo,KT,KH,KW,st,sh,sw,pt,ph,pw,ut,uh,uw) or None
     for a plain linear layer.  `opts` (CallOpts): the operand type of A / W / out_bf16 and the caller's A/B presets for this launch."""
     a = _igemm_args(**{k: v for k, v in locals().items()})
@@ -269,7 +274,7 @@ def igemm(A, W, *, M, N, Cin, lda=None, ldw=None, taps=1, w_tap_stride=0, geom=N
 
 def _igemm_args(A, W, *, M, N, Cin, lda, ldw, taps, w_tap_stride, geom, A_lo, W_lo, bias, rowvec, rows_per_sample, residual, res_period,
                 ld_res, mul, act, alpha, out_f32, out_bf16, out_bf16_lo, ld_out, ld_outb, nbatch, a_batch_stride, w_batch_stride,
-                out_batch_stride, outb_batch_stride, res_batch_stride, tile, debug_flags, splitk_ws, fp8, out_fp8_log2, opts):
+                out_batch_stride, outb_batch_stride, res_batch_stride, tile, debug_flags, splitk_ws, fp8, out_fp8_log2, rowtab, opts):
     """pd_igemm_args of a launch (the keywords of `igemm`)"""
     a = IgemmArgs()
     if opts is not None:
@@ -314,6 +319,10 @@ def _igemm_args(A, W, *, M, N, Cin, lda, ldw, taps, w_tap_stride, geom, A_lo, W_
     a.debug_flags = debug_flags
     a.fp8 = 1 if fp8 else 0           # A / W are e4m3 bytes (torch.float8_e4m3fn); tensor scales in alpha
     a.out_fp8_log2 = out_fp8_log2     # k > 0: out_bf16 is an e4m3 byte tensor receiving e4m3(v * 2^k)
+    if rowtab is not None:          # fp32 (rows, N): out row m += rowtab[m % rows], after the residual (pd_add_rowtable's bits)
+        if rowtab.dim() != 2 or rowtab.shape[1] != N:
+            raise PrediffHipError(f"pd_igemm: the row table must be (rows, N = {N}); got {tuple(rowtab.shape)}")
+        a.rowtab, a.rowtab_rows = ptr(_dev(rowtab, torch.float32)), rowtab.shape[0]
     if splitk_ws is not None:       # fp32 workspace: lets the library split the K loop of small-grid, long-K launches
         a.splitk_ws, a.splitk_ws_elems = ptr(splitk_ws), splitk_ws.numel()
     return a
@@ -351,7 +360,7 @@ def igemm_mx(A, a_scales, W, w_scales, *, M, N, taps=1, geom=None, bias=None, ro
                     W_lo=None, bias=bias, rowvec=rowvec, rows_per_sample=rows_per_sample, residual=residual, res_period=res_period,
                     ld_res=ld_res, mul=mul, act=act, alpha=alpha, out_f32=out_f32, out_bf16=out_bf16, out_bf16_lo=None, ld_out=ld_out,
                     ld_outb=ld_outb, nbatch=1, a_batch_stride=0, w_batch_stride=0, out_batch_stride=0, outb_batch_stride=0,
-                    res_batch_stride=0, tile=0, splitk_ws=splitk_ws, fp8=False, out_fp8_log2=0, opts=None, **presets)
+                    res_batch_stride=0, tile=0, splitk_ws=splitk_ws, fp8=False, out_fp8_log2=0, rowtab=None, opts=None, **presets)
     if opts is not None:
         a.disable_256, a.splitk_max_tiles = 0, opts.igemm_splitk_max_tiles
     m = MxOperands()
@@ -501,6 +510,12 @@ def unet_build_input(x, cond, out, B, T_in, T_out, HW, Cn, ld_out):
            "pd_unet_build_input")
 
 
+def unet_build_input16(x, cond, out, out16, B, T_in, T_out, HW, Cn, ld_out, ld16):
+    """unet_build_input + the bfloat16 copy of its rows (ld16 elements each, zero padded) in one launch"""
+    _check(lib().pd_unet_build_input16(ptr(x), ptr(cond), ptr(out), ptr(_dev(out16, torch.bfloat16)), B, T_in, T_out, HW, Cn, ld_out, ld16,
+                                       stream_ptr()), "pd_unet_build_input16")
+
+
 def timestep_freqs(dim, max_period=10000.0, device="cpu"):
     """exp(-ln(max_period) * arange(half) / half) in fp32, the reference's own expression (models/utils.py:79-81)."""
     import math
@@ -515,6 +530,22 @@ def timestep_embedding(t, freqs, out, B, dim):
 def linear_small(x, W, b, out, M, K, N, act_in="none", act_out="none"):
     _check(lib().pd_linear_small(ptr(x), ptr(W), ptr(b), ptr(out), M, K, N, ACT[act_in], ACT[act_out], stream_ptr()),
            "pd_linear_small")
+
+
+def time_embed_supported(dim, E, nproj):
+    return nproj <= TIME_EMBED_MAX_PROJ and bool(lib().pd_time_embed_supported(dim, E))
+
+
+def time_embed(t, freqs, W0, b0, W2, b2, proj, sin_out, h1, temb, B, dim, E):
+    """The timestep-embedding chain (timestep_embedding, two linear_small, one SiLU-in linear_small per entry of `proj`) in four
+    launches, bit-equal to it.  proj: a list of (W (N, E), b (N,) or None, out (B, N))."""
+    n = len(proj)
+    pw = (C.c_void_p * n)(*[ptr(_dev(w, torch.float32)) for w, _, _ in proj])
+    pb = (C.c_void_p * n)(*[ptr(b) for _, b, _ in proj])
+    po = (C.c_void_p * n)(*[ptr(_dev(o, torch.float32)) for _, _, o in proj])
+    pn = (C.c_int * n)(*[w.shape[0] for w, _, _ in proj])
+    _check(lib().pd_time_embed(ptr(_dev(t, torch.int64)), ptr(freqs), ptr(W0), ptr(b0), ptr(W2), ptr(b2), pw, pb, po, pn, n, ptr(sin_out),
+                               ptr(h1), ptr(temb), B, dim, E, stream_ptr()), "pd_time_embed")
 
 
 def add_rowtable(x, table, n_samples, rows, Cn):

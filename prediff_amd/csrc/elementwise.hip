@@ -10,7 +10,7 @@ extern "C" void pd_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* pd_last_error(void) { return g_err; }
-extern "C" int pd_abi_version(void) { return 4; }   // 2: per-call options (pd_call_opts), IEEE-half operand builds, no exported data symbols; 3: pd_call_opts.small_grid; 4: pd_cuboid_attn_args.qkv_fp8_log2 (was reserved)
+extern "C" int pd_abi_version(void) { return 4; }   // 2: per-call options (pd_call_opts), IEEE-half operand builds, no exported data symbols; 3: pd_call_opts.small_grid; 4: pd_cuboid_attn_args.qkv_fp8_log2 (was reserved); (pd_igemm_args.rowtab at the tail: pd_sizeof_igemm_args tells a stale binding)
 extern "C" int pd_sizeof_igemm_args(void) { return (int)sizeof(pd_igemm_args); }
 extern "C" int pd_sizeof_cuboid_attn_args(void) { return (int)sizeof(pd_cuboid_attn_args); }
 extern "C" int pd_sizeof_call_opts(void) { return (int)sizeof(pd_call_opts); }
@@ -42,6 +42,48 @@ extern "C" int pd_unet_build_input(const float* x, const float* cond, float* out
   PD_CHECK_ARG(x && cond && out && ld_out >= C + 1, "pd_unet_build_input: bad args");
   const int64_t total = (int64_t)B * (T_in + T_out) * HW * ld_out;
   hipLaunchKernelGGL(build_input_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, cond, out, B, T_in, T_out, HW, C, ld_out);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
+// ... and, in the same pass, the bfloat16 copy of those rows that the stem's skip convolution reads (rows of ld16 elements, zero padded):
+// what pd_cast_rows made of `out` in a launch of its own.  A thread moves four channels of one position (16 B loads; the fp32 rows of
+// C + 1 elements are not 16 B aligned: four dword stores) and the four pad columns C + 4 j .. of the 16-bit row, the first of which is
+// the indicator.
+__global__ void __launch_bounds__(256) build_input16_kernel(const float* __restrict__ x, const float* __restrict__ cond, float* __restrict__ out,
+                                                            uint16_t* __restrict__ out16, int B, int T_in, int T_out, int HW, int C, int ld_out,
+                                                            int ld16) {
+  const int T = T_in + T_out, CV = C >> 2;
+  const int64_t total = (int64_t)B * T * HW * CV;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int j = (int)(i % CV);
+    const int64_t pos = i / CV;
+    const int s = (int)(pos % HW);
+    const int t = (int)((pos / HW) % T);
+    const int64_t b = pos / ((int64_t)HW * T);
+    const float4 v = t < T_in ? *(const float4*)(cond + ((b * T_in + t) * HW + s) * C + 4 * j)
+                              : *(const float4*)(x + ((b * T_out + (t - T_in)) * HW + s) * C + 4 * j);
+    const float ind = t < T_in ? 1.f : 0.f;
+    float* o = out + pos * ld_out;
+    o[4 * j] = v.x; o[4 * j + 1] = v.y; o[4 * j + 2] = v.z; o[4 * j + 3] = v.w;
+    if (j == 0) {
+      o[C] = ind;
+      for (int c = C + 1; c < ld_out; ++c) o[c] = 0.f;
+    }
+    uint16_t* o16 = out16 + pos * ld16;
+    *(uint2*)(o16 + 4 * j) = make_uint2(pack_op2(v.x, v.y), pack_op2(v.z, v.w));
+    if (C + 4 * j < ld16) *(uint2*)(o16 + C + 4 * j) = make_uint2(j == 0 ? pack_op2(ind, 0.f) : 0u, 0u);
+  }
+}
+extern "C" int pd_unet_build_input16(const float* x, const float* cond, float* out, pd_bf16* out16, int B, int T_in, int T_out, int HW, int C,
+                                     int ld_out, int ld16, pd_stream_t stream) {
+  PD_CHECK_ARG(x && cond && out && out16 && ld_out >= C + 1, "pd_unet_build_input16: bad args");
+  PD_CHECK_ARG(C > 0 && (C & 3) == 0 && (ld16 & 3) == 0 && ld16 >= C + 1 && ld16 <= 2 * C,
+               "pd_unet_build_input16: C (%d) must be a multiple of 4 and ld16 (%d) one in (C, 2 C]", C, ld16);
+  PD_CHECK_ARG((((uintptr_t)x | (uintptr_t)cond) & 15) == 0 && ((uintptr_t)out16 & 7) == 0, "pd_unet_build_input16: x / cond must be 16 B aligned, out16 8 B");
+  const int64_t total = (int64_t)B * (T_in + T_out) * HW * (C >> 2);
+  hipLaunchKernelGGL(build_input16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, cond, out, out16, B, T_in, T_out, HW, C,
+                     ld_out, ld16);
   PD_CHECK_LAUNCH();
   return PD_OK;
 }
@@ -93,6 +135,141 @@ extern "C" int pd_linear_small(const float* x, const float* W, const float* b, f
                                pd_stream_t stream) {
   PD_CHECK_ARG(x && W && out && M > 0 && M <= 65535 && K > 0 && N > 0, "pd_linear_small: bad args (M=%d)", M);
   hipLaunchKernelGGL(linear_small_kernel, dim3((N + 3) / 4, M), dim3(256), 0, (hipStream_t)stream, x, W, b, out, M, K, N, act_in, act_out);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
+// ---- the timestep-embedding chain in four launches instead of seven (pd_time_embed): sinusoid | Linear + SiLU | Linear | every
+// per-block SiLU -> Linear projection.  linear_small_kernel gives a wave ONE (row, column): at 32 rows a weight row is fetched 32 times
+// and an activation row once per column (268 MB through L2 for the 1024 x 1024 layer), and the input activation is evaluated once per
+// column.  Here a workgroup of eight waves owns eight output columns of one layer for ALL rows: a wave keeps its weight row in registers
+// (K <= 1024: four float4 per lane), and the activation rows pass through LDS in chunks of 32 rows x 256 columns -- staged once per
+// workgroup, the input activation applied on the way in.  The global loads of all four chunks of a row batch are issued together, in
+// front of the first one's use: the kernel is a chain of memory latencies (128 workgroups, a few KB each), and this makes it one.
+// Per (row, column) a lane adds the same products in the same order as linear_small_kernel (k = 4 lane + 256 i, i ascending, the four
+// products of a float4 as contracted there), then the same wave reduction, bias and activation: the outputs are bit-equal to the chain's.
+struct te_job {
+  const float* W;
+  const float* b;
+  float* out;
+  int N, wg0;                                  // output columns; first workgroup of the job (eight columns per workgroup)
+};
+struct te_args {
+  const float* x;                              // (M, K) rows
+  int M, K, njobs;
+  te_job job[PD_TIME_EMBED_MAX_PROJ];
+};
+// ACT_IN / ACT_OUT: PD_ACT_NONE or PD_ACT_SILU, compile-time: the kernel is straight-line code with 96 activation sites, and
+// act_apply's run-time switch at each of them made it 11 000 instructions (88 KB: its time was instruction fetch)
+template <int ACT_IN, int ACT_OUT>
+__global__ void __launch_bounds__(512) linear_rows_kernel(const te_args p) {
+  constexpr int MB = 32, KC = 256, NQ = MB * (KC / 4) / 512;   // rows, columns of a staged chunk (32 KB); float4 per thread and chunk
+  __shared__ float4 sx[MB * (KC / 4)];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int j = 0;
+  for (int q = 1; q < p.njobs; ++q)
+    if ((int)blockIdx.x >= p.job[q].wg0) j = q;
+  const int N = p.job[j].N, K = p.K, M = p.M;
+  const int n = ((int)blockIdx.x - p.job[j].wg0) * 8 + wave;
+  const bool valid = n < N;                    // (a wave past the last column still stages its share of every chunk)
+  const float* __restrict__ w = p.job[j].W + (int64_t)(valid ? n : 0) * K;
+  float* __restrict__ out = p.job[j].out;
+  const float* __restrict__ x = p.x;
+  constexpr int act_in = ACT_IN, act_out = ACT_OUT;
+  float4 wv[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int k = lane * 4 + KC * i;
+    wv[i] = k < K ? *(const float4*)(w + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const float bn = (valid && p.job[j].b) ? p.job[j].b[n] : 0.f;
+  for (int m0 = 0; m0 < M; m0 += MB) {
+    float4 xs[4][NQ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int idx = tid + 512 * q, m = m0 + idx / (KC / 4), k = KC * i + (idx % (KC / 4)) * 4;
+        xs[i][q] = (m < M && k < K) ? *(const float4*)(x + (int64_t)m * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    float acc[MB];
+#pragma unroll
+    for (int r = 0; r < MB; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (KC * i >= K) break;
+      __syncthreads();                         // the previous chunk has been read
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const float4 v = xs[i][q];
+        sx[tid + 512 * q] = make_float4(act_apply(v.x, act_in), act_apply(v.y, act_in), act_apply(v.z, act_in), act_apply(v.w, act_in));
+      }
+      __syncthreads();
+      if (lane * 4 + KC * i < K) {             // (the lanes linear_small_kernel's loop runs for this i)
+        const float4 wq = wv[i];
+#pragma unroll
+        for (int r = 0; r < MB; ++r) {
+          const float4 xq = sx[r * (KC / 4) + lane];
+          // linear_small_kernel's  a += x0 w0 + x1 w1 + x2 w2 + x3 w3  as the compiler contracts it there (one rounded product, three
+          // fused ones, one add), spelled out so that the bits do not depend on how this loop is compiled
+          float t = xq.y * wq.y;
+          t = __builtin_fmaf(xq.x, wq.x, t);
+          t = __builtin_fmaf(xq.z, wq.z, t);
+          t = __builtin_fmaf(xq.w, wq.w, t);
+          acc[r] += t;
+        }
+      }
+    }
+    // wave_sum of every row, level by level: per row the adds of wave_sum in its order, the 32 rows' cross-lane moves of a level in
+    // flight together (row after row they are 192 dependent LDS round trips: most of the kernel's time)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      float u[MB];
+#pragma unroll
+      for (int r = 0; r < MB; ++r) u[r] = __shfl_xor(acc[r], o, 64);
+#pragma unroll
+      for (int r = 0; r < MB; ++r) acc[r] += u[r];
+    }
+    if (lane == 0 && valid) {
+#pragma unroll
+      for (int r = 0; r < MB; ++r)
+        if (m0 + r < M) out[(int64_t)(m0 + r) * N + n] = act_apply(acc[r] + bn, act_out);
+    }
+  }
+}
+
+extern "C" int pd_time_embed_supported(int dim, int E) { return dim > 0 && dim <= 256 && (dim & 3) == 0 && E > 0 && E <= 1024 && (E & 3) == 0; }
+
+extern "C" int pd_time_embed(const int64_t* t, const float* freqs, const float* W0, const float* b0, const float* W2, const float* b2,
+                             const float* const* proj_W, const float* const* proj_b, float* const* proj_out, const int* proj_N, int nproj,
+                             float* sin_out, float* h1, float* temb, int B, int dim, int E, pd_stream_t stream) {
+  PD_CHECK_ARG(t && freqs && W0 && W2 && sin_out && h1 && temb && B > 0, "pd_time_embed: null pointer / bad B (%d)", B);
+  PD_CHECK_ARG(pd_time_embed_supported(dim, E), "pd_time_embed: dim (%d) must be a multiple of 4 up to 256, E (%d) one up to 1024", dim, E);
+  PD_CHECK_ARG(nproj >= 0 && nproj <= PD_TIME_EMBED_MAX_PROJ && (nproj == 0 || (proj_W && proj_b && proj_out && proj_N)),
+               "pd_time_embed: at most %d projections (%d)", PD_TIME_EMBED_MAX_PROJ, nproj);
+  const uintptr_t al = (uintptr_t)freqs | (uintptr_t)W0 | (uintptr_t)W2 | (uintptr_t)sin_out | (uintptr_t)h1 | (uintptr_t)temb;
+  PD_CHECK_ARG((al & 15) == 0, "pd_time_embed: operands must be 16 B aligned");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(timestep_embedding_kernel, dim3((B * dim + 255) / 256), dim3(256), 0, s, t, freqs, sin_out, B, dim);
+  PD_CHECK_LAUNCH();
+  te_args a = {};
+  a.x = sin_out; a.M = B; a.K = dim; a.njobs = 1;
+  a.job[0] = te_job{W0, b0, h1, E, 0};
+  hipLaunchKernelGGL((linear_rows_kernel<PD_ACT_NONE, PD_ACT_SILU>), dim3((E + 7) / 8), dim3(512), 0, s, a);
+  PD_CHECK_LAUNCH();
+  a.x = h1; a.K = E;
+  a.job[0] = te_job{W2, b2, temb, E, 0};
+  hipLaunchKernelGGL((linear_rows_kernel<PD_ACT_NONE, PD_ACT_NONE>), dim3((E + 7) / 8), dim3(512), 0, s, a);
+  PD_CHECK_LAUNCH();
+  if (nproj == 0) return PD_OK;
+  a.x = temb; a.njobs = nproj;
+  int wg = 0;
+  for (int q = 0; q < nproj; ++q) {
+    PD_CHECK_ARG(proj_W[q] && proj_out[q] && proj_N[q] > 0 && ((uintptr_t)proj_W[q] & 15) == 0, "pd_time_embed: projection %d: bad operand", q);
+    a.job[q] = te_job{proj_W[q], proj_b[q], proj_out[q], proj_N[q], wg};
+    wg += (proj_N[q] + 7) / 8;
+  }
+  hipLaunchKernelGGL((linear_rows_kernel<PD_ACT_SILU, PD_ACT_NONE>), dim3(wg), dim3(512), 0, s, a);
   PD_CHECK_LAUNCH();
   return PD_OK;
 }

@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(256, OCC) igemm_kernel(const pd_igemm_args p) 
         for (int r = 0; r < 4; ++r)
           sC[(i * 16 + 4 * lg + r) * WNS + j * 16 + l16] = acc[i][js * TNS + j][r];
     igemm_epilogue_wave_sync();
-    igemm_epilogue<WM, WNS, 4>(p, sC, lane, m0 + wr * WM, p.M, n0 + wc * WN + js * WNS, bz);
+    igemm_epilogue<WM, WNS, 4, false>(p, sC, lane, m0 + wr * WM, p.M, n0 + wc * WN + js * WNS, bz);
   };
   slab(std::integral_constant<int, 0>{});
   if constexpr (ESLAB > 1) slab(std::integral_constant<int, 1>{});
@@ -307,7 +307,7 @@ int pd_igemm_vec_epilogue(const pd_igemm_args& a) {
   const bool v4 = ((a.N & 3) == 0) && (!a.out_f32 || (a.ld_out & 3) == 0) && (!a.out_bf16 || (a.ld_outb & 3) == 0) &&
                   (!a.residual || (a.ld_res & 3) == 0) && (!a.rowvec || (a.ld_rowvec & 3) == 0) &&
                   (!a.mul || (a.ld_mul & 3) == 0) && (((uintptr_t)a.out_f32 | (uintptr_t)a.residual | (uintptr_t)a.rowvec |
-                  (uintptr_t)a.mul) & 15) == 0 && (((uintptr_t)a.out_bf16 | (uintptr_t)a.out_bf16_lo) & 7) == 0 &&
+                  (uintptr_t)a.mul | (uintptr_t)a.rowtab) & 15) == 0 && (((uintptr_t)a.out_bf16 | (uintptr_t)a.out_bf16_lo) & 7) == 0 &&
                   ((a.out_batch_stride | a.outb_batch_stride | a.res_batch_stride) & 3) == 0;
   if (v4 && !a.out_f32 && a.out_bf16 && (a.N & 7) == 0 && (a.ld_outb & 7) == 0 && (a.outb_batch_stride & 7) == 0 &&
       (((uintptr_t)a.out_bf16 | (uintptr_t)a.out_bf16_lo) & 15) == 0)
@@ -346,6 +346,8 @@ extern "C" int PD_ENTRY(igemm)(const pd_igemm_args* pa, pd_stream_t stream) {
   PD_CHECK_ARG(!a.split || (a.A_lo && a.W_lo), "pd_igemm: split needs A_lo and W_lo");
   PD_CHECK_ARG(!a.rowvec || a.rows_per_sample > 0, "pd_igemm: rowvec needs rows_per_sample");
   PD_CHECK_ARG(a.out_f32 || a.out_bf16, "pd_igemm: no output");
+  PD_CHECK_ARG(!a.rowtab || (a.rowtab_rows > 0 && a.out_f32 && !a.out_bf16 && !a.splitk_ws),
+               "pd_igemm: a row table needs rowtab_rows > 0, an fp32 output alone and no split-K workspace");
   hipStream_t s = (hipStream_t)stream;
   a.vec_epilogue = pd_igemm_vec_epilogue(a);
   if (a.out_fp8_log2 > 0) {

@@ -19,6 +19,7 @@ __device__ __forceinline__ void igemm_epilogue_rows(const pd_igemm_args& p, cons
   const bool vec = p.vec_epilogue && (n + CW - 1 < p.N);
   const bool has_rv = on(RV, p.rowvec != nullptr), has_mu = on(MU, p.mul != nullptr), has_rs = on(RS, res != nullptr);
   const bool has_of = on(OF, outf != nullptr), has_ob = on(OB, outb != nullptr), has_ol = on(OL, outbl != nullptr);
+  const bool has_rt = RV == 2 && p.rowtab != nullptr;      // per-row additive table: the run-time (generic) instantiations only
   const int act = ACT >= 0 ? ACT : ((p.debug_flags & 4) ? 0 : p.act);
   float bias_v[CW];
 #pragma unroll
@@ -38,6 +39,7 @@ __device__ __forceinline__ void igemm_epilogue_rows(const pd_igemm_args& p, cons
     const float* rv = has_rv ? p.rowvec + (int64_t)(m / p.rows_per_sample) * p.ld_rowvec + n : nullptr;
     const float* mu = has_mu ? p.mul + (int64_t)m * p.ld_mul + n : nullptr;
     const float* rs = has_rs ? res + (int64_t)(p.res_period ? m % p.res_period : m) * p.ld_res + n : nullptr;
+    const float* rt = has_rt ? p.rowtab + (int64_t)(m % p.rowtab_rows) * p.N + n : nullptr;
     if (vec) {
 #pragma unroll
       for (int e = 0; e < CW; ++e) v[e] = v[e] * p.alpha + bias_v[e];
@@ -60,6 +62,10 @@ __device__ __forceinline__ void igemm_epilogue_rows(const pd_igemm_args& p, cons
       if (has_rs) {
 #pragma unroll
         for (int q = 0; q < CW / 4; ++q) { const float4 t4 = *(const float4*)(rs + 4 * q); v[4 * q] += t4.x; v[4 * q + 1] += t4.y; v[4 * q + 2] += t4.z; v[4 * q + 3] += t4.w; }
+      }
+      if (has_rt) {
+#pragma unroll
+        for (int q = 0; q < CW / 4; ++q) { const float4 t4 = *(const float4*)(rt + 4 * q); v[4 * q] += t4.x; v[4 * q + 1] += t4.y; v[4 * q + 2] += t4.z; v[4 * q + 3] += t4.w; }
       }
       if (has_of) {
 #pragma unroll
@@ -109,6 +115,7 @@ __device__ __forceinline__ void igemm_epilogue_rows(const pd_igemm_args& p, cons
         x = (has_ob && !has_ol && !has_of) ? act_apply16(x, act) : act_apply(x, act);
         if (mu) x *= mu[e];
         if (rs) x += rs[e];
+        if (rt) x += rt[e];
         if (has_of) outf[(int64_t)m * p.ld_out + n + e] = x;
         if (has_ob) {
           uint16_t h, l;
@@ -137,14 +144,18 @@ __device__ __forceinline__ void igemm_epilogue_rows(const pd_igemm_args& p, cons
 // one with the fewest registers stays: a wave has 8 loads + 4 stores of 1 KB in flight.  (-DPD_EPI_R=n builds another for A/B runs.)
 #define PD_EPI_R 4
 #endif
-template <int WM, int WNS, int RV, int RS, int R>
+//  - TB: the per-row additive table (row m % rowtab_rows of p.rowtab, N columns; with the residual form only) is a second operand stream,
+//    loaded with the residual's and added after it: ((acc * alpha + bias) + residual) + table, the order of a pd_add_rowtable launch
+//    behind the convolution.
+template <int WM, int WNS, int RV, int RS, int R, bool TB = false>
 __device__ __forceinline__ void igemm_epilogue_rows_f32(const pd_igemm_args& p, const float* sC, int lane, int m_base, int m_end, int n_base,
                                                         float* outf, const float* res) {
   static_assert(RV + RS == 1, "one global operand: the per-sample row vector or the residual");
   constexpr int LPR = WNS / 4;                     // lanes per row
   constexpr int RPP = 64 / LPR;                    // rows per pass
   constexpr int NP = WM / RPP;                     // passes per slab
-  static_assert(NP % R == 0 && 3 * R < 63, "whole batches; loads + stores in flight fit the vmcnt field");
+  static_assert(NP % R == 0 && (TB ? 5 : 3) * R < 63, "whole batches; loads + stores in flight fit the vmcnt field");
+  static_assert(!TB || RS, "the row table goes with the residual form");
   constexpr int NB = NP / R;
   if (m_base >= m_end) return;
   const int c0 = (lane % LPR) * 4;
@@ -160,11 +171,15 @@ __device__ __forceinline__ void igemm_epilogue_rows_f32(const pd_igemm_args& p, 
     constexpr bool FULL = decltype(full)::value;     // every row of the slab is stored: no lane predicate round the stores
     float4 rv0 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (UNI) rv0 = *(const float4*)(p.rowvec + (int64_t)(m_base / p.rows_per_sample) * p.ld_rowvec + n);
-    auto issue = [&](int b, float4(&d)[R]) {
+    auto issue = [&](int b, float4(&d)[R], float4(&dt)[TB ? R : 1]) {
       if (UNI) return;
       int src[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) src[r] = FULL ? m_base + (b * R + r) * RPP + row0 : min(m_base + (b * R + r) * RPP + row0, m_last);
+      if constexpr (TB) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) dt[r] = *(const float4*)(p.rowtab + (int64_t)(src[r] % p.rowtab_rows) * p.N + n);
+      }
       if (RS) {
         if (p.res_period) {
 #pragma unroll
@@ -179,11 +194,11 @@ __device__ __forceinline__ void igemm_epilogue_rows_f32(const pd_igemm_args& p, 
 #pragma unroll
       for (int r = 0; r < R; ++r) d[r] = *(const float4*)(base + (int64_t)src[r] * ld);
     };
-    float4 g[2][R];
-    issue(0, g[0]);
+    float4 g[2][R], gt[2][TB ? R : 1];
+    issue(0, g[0], gt[0]);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-      if (b + 1 < NB) issue(b + 1, g[(b + 1) & 1]);
+      if (b + 1 < NB) issue(b + 1, g[(b + 1) & 1], gt[(b + 1) & 1]);
       float4 v[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) v[r] = *(const float4*)(sC + ((b * R + r) * RPP + row0) * WNS + c0);
@@ -194,6 +209,10 @@ __device__ __forceinline__ void igemm_epilogue_rows_f32(const pd_igemm_args& p, 
         v[r].y = __builtin_fmaf(v[r].y, alpha, bias_v[1]) + t4.y;
         v[r].z = __builtin_fmaf(v[r].z, alpha, bias_v[2]) + t4.z;
         v[r].w = __builtin_fmaf(v[r].w, alpha, bias_v[3]) + t4.w;
+        if constexpr (TB) {
+          const float4 u4 = gt[b & 1][r];
+          v[r].x += u4.x; v[r].y += u4.y; v[r].z += u4.z; v[r].w += u4.w;
+        }
         // the value exists here, for every lane: the arithmetic (and with it the counted wait for the operand load) must not sink into the
         // predicated store below, where a lane-masked wait would be repeated, as vmcnt(0), in front of every later store
         asm volatile("" : "+v"(v[r].x), "+v"(v[r].y), "+v"(v[r].z), "+v"(v[r].w));
@@ -224,7 +243,8 @@ __device__ __forceinline__ void igemm_epilogue_wave_sync() { asm volatile("s_wai
 
 // sC: this wave's WM x WNS fp32 slab; (m_base, n_base): its position in the output; rows >= m_end are not stored; bz: batched-GEMM index.
 // RMAX: the most passes per batch the calling kernel has registers for (no kernel may gain scratch); 0 = it keeps the serial loop.
-template <int WM, int WNS, int RMAX = PD_EPI_R>
+// TBP: the kernel also has the registers for the pipelined row-table form (a second operand stream); else a table takes the serial loop.
+template <int WM, int WNS, int RMAX = PD_EPI_R, bool TBP = true>
 __device__ __forceinline__ void igemm_epilogue(const pd_igemm_args& p, const float* sC, int lane, int m_base, int m_end, int n_base, int bz) {
   float* outf = p.out_f32 ? p.out_f32 + (int64_t)bz * p.out_batch_stride : nullptr;
   pd_bf16* outb = p.out_bf16 ? p.out_bf16 + (int64_t)bz * p.outb_batch_stride : nullptr;
@@ -233,18 +253,22 @@ __device__ __forceinline__ void igemm_epilogue(const pd_igemm_args& p, const flo
   const bool rvp = p.rowvec != nullptr, mup = p.mul != nullptr, rsp = res != nullptr, ofp = outf != nullptr, obp = outb != nullptr,
              olp = outbl != nullptr;
   const int actv = (p.debug_flags & 4) ? 0 : p.act;
+  const bool rtp = p.rowtab != nullptr;              // (only the residual-stream writers with a residual have a compiled form of their own for it)
   constexpr int GELU = PD_ACT_GELU;
-  if (p.vec_epilogue == 2 && !rvp && !mup && !rsp && !ofp && obp && !olp && (actv == 0 || actv == GELU)) {
+  if (p.vec_epilogue == 2 && !rtp && !rvp && !mup && !rsp && !ofp && obp && !olp && (actv == 0 || actv == GELU)) {
     // bf16-only producers: QKV (no activation), FFN-1 (GELU)
     if (actv == 0) igemm_epilogue_rows<WM, WNS, 8, 0, 0, 0, 0, 0, 1, 0>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
     else igemm_epilogue_rows<WM, WNS, 8, GELU, 0, 0, 0, 0, 1, 0>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
-  } else if (p.vec_epilogue && ofp && !obp && !mup && actv == 0 && (rsp != rvp)) {
+  } else if (p.vec_epilogue && ofp && !obp && !mup && actv == 0 && (rsp != rvp) && (!rtp || rsp)) {
     // fp32 residual-stream writers: proj / FFN-2 / conv-2 (+residual), conv-1 (+timestep embedding)
     // (pipelined unless debug_flags bit 32 asks for the serial loop; a lane whose four columns cross N takes the scalar path of that loop)
     constexpr int NP = WM / (64 / (WNS / 4));
     constexpr int R = RMAX == 0 ? 1 : RMAX < NP ? RMAX : NP;
     const bool serial = RMAX == 0 || (p.debug_flags & 32) || n_base + (lane % (WNS / 4)) * 4 + 3 >= p.N;
-    if (rsp) {
+    if (rsp && rtp) {
+      if (serial || !TBP) igemm_epilogue_rows<WM, WNS, 4, -1, 2, 2, 2, 2, 2, 2>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
+      else if (!(p.debug_flags & 2)) igemm_epilogue_rows_f32<WM, WNS, 0, 1, R, TBP>(p, sC, lane, m_base, m_end, n_base, outf, res);
+    } else if (rsp) {
       if (serial) igemm_epilogue_rows<WM, WNS, 4, 0, 0, 0, 1, 1, 0, 0>(p, sC, lane, m_base, m_end, n_base, outf, outb, outbl, res);
       else if (!(p.debug_flags & 2)) igemm_epilogue_rows_f32<WM, WNS, 0, 1, R>(p, sC, lane, m_base, m_end, n_base, outf, res);
     } else {

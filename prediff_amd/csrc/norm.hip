@@ -631,6 +631,111 @@ static void gn_onepass_launch(const float* x, const float* gamma, const float* b
 #undef GN1P
 }
 
+// ---- one pass for narrow rows whose channel count the kernels above cannot take (the stem of the denoiser: C = 65, one group per channel;
+// before: the scalar statistics + apply pair of launches).  A workgroup owns (sample, up to 16 channels holding whole groups) and keeps its
+// S x 16 values in registers, one per (row lane, channel slot) and sweep: 32 rows per sweep, RMAX sweeps (104: up to 3328 rows).  Rows are
+// not 16 B aligned (C is odd), so the loads are single dwords through a buffer descriptor (no address registers per load; rows >= S and
+// the slots past the workgroup's channels get an out-of-range lane offset: zeros).  Statistics in the one-pass kernel's form -- fp32 mean,
+// then the centred sum of squares -- reduced over the four row lanes of a wave by shuffles, then over the waves and the group's slots
+// through LDS in a fixed order.  `partials` as gn_onepass_kernel writes it.  The pad columns [C, ld_out) are zeroed, each of the
+// sample's workgroups taking every nsplit-th row.
+template <int RMAX>
+__global__ void __launch_bounds__(512) gn_narrow_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, const float* __restrict__ ss_scale,
+                                                        const float* __restrict__ ss_shift, int ld_ss, double* __restrict__ partials,
+                                                        int nchunk, pd_bf16* __restrict__ out, int S, int C, int G, int ld_out, float eps,
+                                                        int silu, int gpw, int nsplit) {
+  constexpr int NWV = 8, RP = 32;
+  __shared__ float sred[2][NWV][16];
+  const int b = blockIdx.x / nsplit, part = blockIdx.x - b * nsplit;
+  const int cpg = C / G;
+  const int g0 = part * gpw, g1 = min(G, g0 + gpw);
+  const int c0 = g0 * cpg, nch = (g1 - g0) * cpg;                    // this workgroup's channels: [c0, c0 + nch), nch <= 16
+  const int tid = threadIdx.x, slot = tid & 15, rl = tid >> 4, wave = tid >> 6;
+  const bool active = slot < nch;
+  const int c = c0 + (active ? slot : 0);
+  const int gl = (active ? slot : 0) / cpg;                          // the thread's group, local
+  const auto rX = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (int64_t)b * S * C), 0, (uint32_t)((int64_t)S * C * 4), 0x00020000);
+  const uint32_t voff = (uint32_t)(rl * C + c) * 4u, sstep = (uint32_t)(RP * C) * 4u;
+  constexpr uint32_t GN_OOB = 0xFFFFF000u;
+  float v[RMAX];
+#pragma unroll
+  for (int i = 0; i < RMAX; ++i)
+    v[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rX, (active && rl + RP * i < S) ? voff : GN_OOB, (uint32_t)i * sstep, 0));
+  auto group_sum = [&](float t, int buf) {
+    t += __shfl_xor(t, 16);
+    t += __shfl_xor(t, 32);
+    if ((tid & 63) < 16) sred[buf][wave][slot] = t;
+    __syncthreads();
+    float tot = 0.f;
+    for (int w = 0; w < NWV; ++w)
+      for (int k = 0; k < cpg; ++k) tot += sred[buf][w][gl * cpg + k];
+    return tot;
+  };
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < RMAX; ++i) s += v[i];
+  const float cnt = (float)S * (float)cpg;
+  const float mean = group_sum(s, 0) / cnt;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < RMAX; ++i) {
+    if (rl + RP * i < S) {
+      const float d0 = v[i] - mean;
+      q += d0 * d0;
+    }
+  }
+  const float var = group_sum(active ? q : 0.f, 1) / cnt;
+  const float rstd = 1.0f / sqrtf(var + eps);
+  if (active && rl == 0 && slot % cpg == 0) {
+    double* pp = partials + (int64_t)b * nchunk * G * 2 + (g0 + gl) * 2;
+    pp[0] = (double)mean * (double)cnt;
+    pp[1] = ((double)var + (double)mean * (double)mean) * (double)cnt;
+    for (int k = 1; k < nchunk; ++k) { pp[(int64_t)k * G * 2] = 0.0; pp[(int64_t)k * G * 2 + 1] = 0.0; }
+  }
+  float a = 0.f, d = 0.f;
+  if (active) {
+    a = rstd * gamma[c];
+    d = beta[c] - mean * a;
+    if (ss_scale) {
+      const float sc = ss_scale[(int64_t)b * ld_ss + c], sh = ss_shift[(int64_t)b * ld_ss + c];
+      a *= (1.f + sc);
+      d = d * (1.f + sc) + sh;
+    }
+  }
+  pd_bf16* ob = out + (int64_t)b * S * ld_out;
+#pragma unroll
+  for (int i = 0; i < RMAX; ++i) {
+    const int r = rl + RP * i;
+    float y = v[i] * a + d;
+    if (silu) y = y / (1.f + __expf(-y));
+    if (active && r < S) ob[(int64_t)r * ld_out + c] = f2op(y);
+  }
+  const int npad = ld_out - C;
+  if (npad > 0) {
+    const int rows = (S - part + nsplit - 1) / nsplit;               // rows part, part + nsplit, ...
+    for (int i = tid; i < rows * npad; i += 512) {
+      const int j = i / npad, pc = i - j * npad;
+      ob[(int64_t)(part + j * nsplit) * ld_out + C + pc] = 0;
+    }
+  }
+}
+// Shapes of the narrow one-pass kernel: what the vectorised kernels refuse, rows of at most 128 channels, groups of at most 16, at most
+// 104 x 32 rows -- and at least 8 x 32: a sample of fewer rows leaves most of the 512 threads' sweeps empty (70 rows: three sweeps, the
+// third a fifth full), there the statistics + apply pair stays
+static bool gn_narrow_fits(int S, int C, int G) { return C <= 128 && C / G <= 16 && S >= 32 * 8 && S <= 32 * 104; }
+static void gn_narrow_launch(const float* x, const float* gamma, const float* beta, const float* ss_scale, const float* ss_shift, int ld_ss,
+                             double* partials, int nchunk, pd_bf16* out, int B, int S, int C, int G, int ld_out, float eps, int silu,
+                             hipStream_t s) {
+  const int cpg = C / G;
+  const int nsplit = (G + 16 / cpg - 1) / (16 / cpg), gpw = (G + nsplit - 1) / nsplit;   // workgroups per sample, evenly filled (65 groups of one: 5 x 13)
+#define GNNR(RM) hipLaunchKernelGGL((gn_narrow_kernel<RM>), dim3(B * nsplit), dim3(512), 0, s, x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, \
+                                    nchunk, out, S, C, G, ld_out, eps, silu, gpw, nsplit)
+  if (S <= 32 * 26) GNNR(26);
+  else GNNR(104);
+#undef GNNR
+}
+
 // Shapes and pointers of the vectorised kernels (gn_stats_vec_kernel, gn_apply_vec_kernel): a thread owns one float4 column of ONE group,
 // 256 threads hold whole rows.  gamma / beta / scale-shift may be null where the caller has none.  The output's own conditions (alignment
 // of its packed store, dense rows) are the caller's.
@@ -678,6 +783,12 @@ extern "C" int PD_ENTRY(groupnorm_silu)(const float* x, const float* gamma, cons
     return PD_OK;
   }
   if (vec) return gn_two_pass<Out::Op16>(x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, out, out_lo, B, S, C, G, ld_out, eps, silu, 1.f, s);
+  // narrow rows the vectorised kernels cannot take (C = 65: the stem), bf16 engine: one launch, everything of a (sample, 16 channels) in registers
+  if (onepass && !out_lo && gn_narrow_fits(S, C, G)) {
+    gn_narrow_launch(x, gamma, beta, ss_scale, ss_shift, ld_ss, partials, nchunk, out, B, S, C, G, ld_out, eps, silu, s);
+    PD_CHECK_LAUNCH();
+    return PD_OK;
+  }
   hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, B), dim3(256), (512 + 2 * G) * sizeof(double), s, x, partials, S, C, G);
   PD_CHECK_LAUNCH();
   hipLaunchKernelGGL(gn_apply_kernel, dim3(nchunk, B), dim3(256), 2 * G * sizeof(float), s, x, gamma, beta, ss_scale, ss_shift,
@@ -855,6 +966,27 @@ __global__ void __launch_bounds__(256) cast_rows_kernel(const float* __restrict_
   }
 }
 
+// ... four columns per thread (16 B loads, 8 B stores) where the rows allow it: C, ld_in, ld_out multiples of 4, no low halves.  The same
+// round-to-nearest-even values as the scalar kernel's (which moves 2 B per lane and divides twice per element: 29 us for the 50 MB of the
+// denoiser's head input, six times the time its bytes need).
+__global__ void __launch_bounds__(256) cast_rows_vec_kernel(const float* __restrict__ x, pd_bf16* __restrict__ out, int64_t n_out_rows, int rows_in,
+                                                            int row_off, int rows_out, int C, int ld_in, int ld_out) {
+  const int lv = ld_out >> 2;
+  const int64_t total = n_out_rows * lv;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t ro = i / lv;
+    const int c = (int)(i - ro * lv) * 4;
+    const int64_t smp = ro / rows_out;
+    const int r = (int)(ro - smp * rows_out);
+    float y[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c < C) {
+      const float4 v = *(const float4*)(x + (smp * rows_in + row_off + r) * (int64_t)ld_in + c);
+      y[0] = v.x; y[1] = v.y; y[2] = v.z; y[3] = v.w;
+    }
+    *(uint2*)(out + ro * ld_out + c) = pack_op4(y);
+  }
+}
+
 extern "C" int PD_ENTRY(cast_rows)(const float* x, pd_bf16* out, pd_bf16* out_lo, int64_t n_samples, int rows_per_sample_in, int row_off,
                                    int rows_per_sample_out, int C, int ld_in, int ld_out, const pd_call_opts* opts, pd_stream_t stream) {
   PD_FORWARD_F16(PD_OPTS_F16(opts), pd_f16_cast_rows(x, out, out_lo, n_samples, rows_per_sample_in, row_off, rows_per_sample_out, C, ld_in,
@@ -865,6 +997,13 @@ extern "C" int PD_ENTRY(cast_rows)(const float* x, pd_bf16* out, pd_bf16* out_lo
   const int64_t rows = n_samples * rows_per_sample_out;
   if (rows <= 0) return PD_OK;
   const int64_t total = rows * ld_out;
+  if (!out_lo && ((C | ld_in | ld_out) & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 7) == 0) {
+    const unsigned gridv = (unsigned)min((int64_t)8192, (total / 4 + 255) / 256);
+    hipLaunchKernelGGL(cast_rows_vec_kernel, dim3(gridv), dim3(256), 0, (hipStream_t)stream, x, out, rows, rows_per_sample_in, row_off,
+                       rows_per_sample_out, C, ld_in, ld_out);
+    PD_CHECK_LAUNCH();
+    return PD_OK;
+  }
   const unsigned grid = (unsigned)min((int64_t)4096, (total + 255) / 256);
   hipLaunchKernelGGL(cast_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, out, out_lo, rows, rows_per_sample_in, row_off,
                      rows_per_sample_out, C, ld_in, ld_out);

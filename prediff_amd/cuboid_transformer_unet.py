@@ -390,6 +390,14 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         # (pd_attn_ffn_pair_split; only with split_k: its fp32 summation order is not the one-launch kernel's)
         self.pair_split = os.environ.get("PD_PAIR_SPLIT", "1") != "0"
         self.split_k = True           # bf16 mode, <= 16 trajectories per launch: split-K Conv3d (K-slices as extra workgroups)
+        # the glue of the step folded into its neighbours; each switch off = the launches it replaces (A/B runs; the same bits either way)
+        self.fuse_time_embed = True   # pd_time_embed: the timestep-embedding chain in four launches instead of seven
+        self.fuse_input_cast = True   # pd_unet_build_input16: the stem's input rows and their 16-bit copy (the skip convolution's operand) in one launch
+        self.fuse_pos_epilogue = True # the positional table in first_proj's conv-2 epilogue instead of a pd_add_rowtable launch behind it
+        # the last decoder stack: its trailing (attention, FFN) pairs whose cuboids lie inside one frame (H axis, W axis) run over the
+        # target frames' cuboids only -- the head reads no other row, and such a pair moves nothing between frames
+        self.tail_target_only = True
+        self.skip_no_copy = True      # the up-sampling conv writes `X{i}.up`: the encoder's X{i} IS the U-Net skip, no copy of it
         self.input_shape, self.target_shape = input_shape, target_shape
         self.num_blocks = len(depth)
         self.depth = list(depth)
@@ -679,6 +687,17 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
             self._tables_dev[device] = [[dict(tok=g["tok_index"].to(device), mask=(g["mask"].to(device) if g["mask"] is not None else None),
                                               tok_out=(g["tok_out"].to(device) if g.get("tok_out") is not None else None))
                                          for g in lvl] for lvl in self._geom]
+            # level 0, tail_target_only: per attention layer the sub-table of the cuboids of the frames >= in_len, where every cuboid of the
+            # layer lies inside one frame; from the first layer on after which all layers are such (an earlier one may feed a frame-mixing one)
+            T, H, W, _ = self.data_shape
+            first = len(self._geom[0])
+            for a in range(len(self._geom[0]) - 1, -1, -1):
+                frame = torch.div(self._geom[0][a]["tok_index"].long().clamp_min(0), H * W, rounding_mode="floor")
+                if self._geom[0][a]["tok_out"] is not None or not bool((frame == frame[:, :1]).all()):
+                    break
+                first = a
+                keep = frame[:, 0] >= self.in_len
+                self._tables_dev[device][0][a]["tok_tail"] = self._geom[0][a]["tok_index"][keep].contiguous().to(device)
 
     def pack(self, device=None):
         """Pack the weights now (otherwise done lazily at the first forward and after every weight update)."""
@@ -766,8 +785,10 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         L.layernorm(x, g, beta, *a, rows, C, ld, opts=self.opts)
         return Act(*a, ld)
 
-    def _resblock(self, P, name, m: TimeEmbedResBlock, x, B, thw, emb, dev, out=None):
-        """TimeEmbedResBlock.forward (models/time_embed.py:134-169) on channels-last fp32 x (B*S, Cin)."""
+    def _resblock(self, P, name, m: TimeEmbedResBlock, x, B, thw, emb, dev, out=None, rowtab=None, x16=None):
+        """TimeEmbedResBlock.forward (models/time_embed.py:134-169) on channels-last fp32 x (B*S, Cin).  rowtab: an (S, Cout) fp32 table
+        added to every sample's rows of the result, in the second convolution's epilogue.  x16: x as 16-bit operand rows (an Act), where
+        the caller has them already (else the skip convolution's operand is cast here)."""
         T, H, W = thw
         S = T * H * W
         ws = self._splitk_ws(B, dev)
@@ -786,10 +807,11 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
         else:
             # 1x1x1 (or 3x3x3 when use_conv) skip on the raw input, written to `out`, then accumulated into by conv2
             k = m.skip_connection.kernel_size[0]
-            self._gemm(P, name + ".skip", self._cast(x, "skip.a", S, Cin, dev, samples=B), M=B * S, N=Cout, taps=k ** 3,
+            self._gemm(P, name + ".skip", x16 if x16 is not None else self._cast(x, "skip.a", S, Cin, dev, samples=B), M=B * S, N=Cout, taps=k ** 3,
                        geom=L.conv_geom(B, thw, (k, k, k), pad=(k // 2,) * 3), out_f32=out)
             res = out
-        self._gemm(P, name + ".conv2", a2, M=B * S, N=Cout, taps=27, geom=geom, residual=res, out_f32=out, splitk_ws=ws)
+        self._gemm(P, name + ".conv2", a2, M=B * S, N=Cout, taps=27, geom=geom, residual=res, out_f32=out, splitk_ws=ws,
+                   **(dict(rowtab=rowtab) if rowtab is not None else {}))
         return out
 
     def _patch_merge(self, P, name, dl: PatchMerging3D, x, B, thw, Cp, Cout, ds, out, dev):
@@ -900,8 +922,9 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
             self._gemm(P, name + ".fc1", a, M=rows, N=Hd, **hidden)
         self._gemm(P, name + ".fc2", h, M=rows, N=C, residual=x, out_f32=x)
 
-    def _stack(self, P, name, blk: StackCuboidSelfAttentionBlock, x, B, S, C, level, dev):
-        """StackCuboidSelfAttentionBlock.forward, eval branch (cuboid_transformer.py:1147-1156 / 1176-1186)."""
+    def _stack(self, P, name, blk: StackCuboidSelfAttentionBlock, x, B, S, C, level, dev, tail=False):
+        """StackCuboidSelfAttentionBlock.forward, eval branch (cuboid_transformer.py:1147-1156 / 1176-1186).  tail: only the rows of the
+        target frames are read after this block (level 0): the pair launches that have a `tok_tail` table run over it."""
         tabs = self._tables_dev[dev][level]
         for a, at in enumerate(blk.attn_l):
             if self.w_fold:
@@ -915,6 +938,11 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
             enough = (groups + 7) // 8 >= self.pair_min_tiles if C == 256 else (groups + 3) // 4 >= self.pair_l1_min_tiles
             if pair is not None and C in self.pair_units and (enough or not self.split_k):
                 # x += attn(x); x = ffn(x) in one launch, rows register resident (csrc/pair_block.hip)
+                sub = tabs[a].get("tok_tail") if (tail and self.tail_target_only and blk.use_inter_ffn) else None
+                if sub is not None:      # (table mode: the affine form has no base offset)
+                    L.attn_ffn_pair(x, x, pair[0], pair[1], sub, B, S, sub.shape[0], geo["vol"], float(at.scale), eps_attn=pair[2],
+                                    eps_ffn=pair[3], units=C, opts=self.opts)
+                    continue
                 L.attn_ffn_pair(x, x, pair[0], pair[1], tabs[a]["tok"], B, S, geo["nc"], geo["vol"], float(at.scale), eps_attn=pair[2],
                                 eps_ffn=pair[3], tok_affine=geo.get("affine"), units=C, opts=self.opts)
                 continue
@@ -958,26 +986,39 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
 
         # ---- stem: concat + indicator, first_proj resblock, positional table ----
         xin = self._buf("xin", (B * S0, Cd), torch.float32, dev)
-        L.unet_build_input(x, cond, xin, B, self.in_len, self.out_len, H * W, C_lat, Cd)
+        xin16 = None
+        if (self.fuse_input_cast and self.precision == "bf16" and self.operand == "bf16" and not isinstance(self.first_proj.skip_connection, nn.Identity)
+                and C_lat % 4 == 0 and pad64(Cd) <= 2 * C_lat and (x.data_ptr() | cond.data_ptr()) % 16 == 0):
+            xin16 = Act(self._buf("skip.a", (B * S0, pad64(Cd)), self.op_dtype, dev), None, pad64(Cd))
+            L.unet_build_input16(x, cond, xin, xin16.hi, B, self.in_len, self.out_len, H * W, C_lat, Cd, xin16.ld)
+        else:
+            L.unet_build_input(x, cond, xin, B, self.in_len, self.out_len, H * W, C_lat, Cd)
         X = self._buf("X0", (B * S0, C0), torch.float32, dev)
-        self._resblock(P, "first", self.first_proj, xin, B, (T, H, W), None, dev, out=X)
-        L.add_rowtable(X, P["pos"], B, S0, C0)
+        # (the table rides in conv-2's epilogue -- ((acc + bias) + skip) + pos, the bits of the launch it replaces -- unless the launch may be
+        #  K-split (small batches: the reduce kernel has no table) or runs on MX operands)
+        pos_fused = self.fuse_pos_epilogue and self._splitk_ws(B, dev) is None and "first.conv2.wmx" not in P
+        self._resblock(P, "first", self.first_proj, xin, B, (T, H, W), None, dev, out=X, rowtab=P["pos"] if pos_fused else None, x16=xin16)
+        if not pos_fused:
+            L.add_rowtable(X, P["pos"], B, S0, C0)
 
         # ---- timestep embedding: sinusoid -> MLP -> one projection per TimeEmbedResBlock module ----
         E = self.time_embed_channels
         sin = self._buf("te.sin", (B, self.block_units[0]), torch.float32, dev)
-        L.timestep_embedding(t, P["te.freqs"], sin, B, self.block_units[0])
         h1 = self._buf("te.h1", (B, E), torch.float32, dev)
-        L.linear_small(sin, P["te.w0"], P["te.b0"], h1, B, self.block_units[0], E, act_out="silu")
         temb = self._buf("te.out", (B, E), torch.float32, dev)
-        L.linear_small(h1, P["te.w2"], P["te.b2"], temb, B, E, E)
         embs = {}
         for i in range(self.num_blocks):
             for tag, m in (("dte", self.down_time_embed_blocks[i]), ("ute", self.up_time_embed_blocks[i])):
-                n = m.emb_layers[1].out_features
-                e = self._buf(f"te.{tag}{i}", (B, n), torch.float32, dev)
-                L.linear_small(temb, P[f"{tag}{i}.emb.w"], P[f"{tag}{i}.emb.b"], e, B, E, n, act_in="silu")
-                embs[f"{tag}{i}"] = e
+                embs[f"{tag}{i}"] = self._buf(f"te.{tag}{i}", (B, m.emb_layers[1].out_features), torch.float32, dev)
+        if self.fuse_time_embed and L.time_embed_supported(self.block_units[0], E, len(embs)):
+            L.time_embed(t, P["te.freqs"], P["te.w0"], P["te.b0"], P["te.w2"], P["te.b2"],
+                         [(P[f"{k}.emb.w"], P[f"{k}.emb.b"], e) for k, e in embs.items()], sin, h1, temb, B, self.block_units[0], E)
+        else:
+            L.timestep_embedding(t, P["te.freqs"], sin, B, self.block_units[0])
+            L.linear_small(sin, P["te.w0"], P["te.b0"], h1, B, self.block_units[0], E, act_out="silu")
+            L.linear_small(h1, P["te.w2"], P["te.b2"], temb, B, E, E)
+            for k, e in embs.items():
+                L.linear_small(temb, P[f"{k}.emb.w"], P[f"{k}.emb.b"], e, B, E, e.shape[1], act_in="silu")
 
         # ---- encoder ----
         shapes = self.mem_shapes
@@ -997,8 +1038,11 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
                 self._resblock(P, f"dte{i}", self.down_time_embed_blocks[i], cur, B, (Ti, Hi, Wi), embs[f"dte{i}"], dev)
                 self._stack(P, f"ds{i}.{d}", self.down_self_blocks[i][d], cur, B, Si, Ci, i, dev)
             if self.unet_res_connect and i < self.num_blocks - 1:
-                sk = self._buf(f"skip{i}", (B * Si, Ci), torch.float32, dev)
-                sk.copy_(cur)
+                if self.skip_no_copy:      # nothing writes X{i} again: the decoder's level i lives in `X{i}.up`
+                    sk = cur
+                else:
+                    sk = self._buf(f"skip{i}", (B * Si, Ci), torch.float32, dev)
+                    sk.copy_(cur)
                 skips.append(sk)
         # ---- decoder ----
         for i in range(self.num_blocks - 1, -1, -1):
@@ -1006,10 +1050,10 @@ class CuboidTransformerUNet(nn.Module, HipEngine):
             Si = Ti * Hi * Wi
             for d in range(self.depth[i]):
                 self._resblock(P, f"ute{i}", self.up_time_embed_blocks[i], cur, B, (Ti, Hi, Wi), embs[f"ute{i}"], dev)
-                self._stack(P, f"us{i}.{d}", self.up_self_blocks[i][d], cur, B, Si, Ci, i, dev)
+                self._stack(P, f"us{i}.{d}", self.up_self_blocks[i][d], cur, B, Si, Ci, i, dev, tail=(i == 0 and d == self.depth[0] - 1))
             if i > 0:
                 Tn, Hn, Wn, Cn = shapes[i - 1]
-                nxt = self._buf(f"X{i - 1}", (B * Tn * Hn * Wn, Cn), torch.float32, dev)
+                nxt = self._buf(f"X{i - 1}.up" if self.skip_no_copy else f"X{i - 1}", (B * Tn * Hn * Wn, Cn), torch.float32, dev)
                 # next level starts with `x = x + skip` (:473-474): fused as the residual of the up-sampling conv
                 res = skips[i - 1] if self.unet_res_connect else None
                 self._upsample(P, f"up{i - 1}", cur, B, (Ti, Hi, Wi), Ci, (Hn, Wn), Cn, self.upsample_kernel_size, res, nxt, dev)
