@@ -97,8 +97,8 @@ __global__ void __launch_bounds__(ST_THREADS) anvil_spectra_kernel(const float* 
   const float l0 = (float)j0, l1 = (float)j1;
 
   double s[1] = {0.0};
-  ST_PIXELS(const float a0 = q == 0 ? f0[i] : st_bil_fill(f0, H, W, (float)y - l0 * vy[i], (float)x - l0 * vx[i]);
-            const float a1 = two ? st_bil_fill(f1, H, W, (float)y - l1 * vy[i], (float)x - l1 * vx[i]) : 0.f;
+  ST_PIXELS(const float a0 = q == 0 ? f0[i] : bil_fill(f0, H, W, (float)y - l0 * vy[i], (float)x - l0 * vx[i], 0.f);
+            const float a1 = two ? bil_fill(f1, H, W, (float)y - l1 * vy[i], (float)x - l1 * vx[i], 0.f) : 0.f;
             z[li] = make_float2(a0, a1); s[0] += (double)a0 * (double)a0;)
   if (q == 0) {
     block_sum<1>(s, red);
@@ -247,7 +247,7 @@ extern "C" int64_t pd_anvil_ws_bytes(int64_t B, int H, int W, int levels, int ar
   PD_CHECK_ARG(an_layout(B, H, W, levels, ar, g),                                                                                           \
                who ": unsupported shape or options (%lld sequences, frames %d x %d, levels=%d, ar_order=%d): sides 2^a or 3 * 2^a, "        \
                    "%d .. %d, H W <= %d; 2 <= levels <= floor(log2(max(H, W))) - 1; ar_order 1 or 2; B <= %d",                               \
-               (long long)(B), H, W, levels, ar, ST_MIN_SIDE, ST_MAX_SIDE, ST_MAX_ELEMS, ST_MAX_BATCH)
+               (long long)(B), H, W, levels, ar, SP_MIN_SIDE, SP_MAX_SIDE, ST_MAX_ELEMS, ST_MAX_BATCH)
 
 extern "C" int pd_anvil_analyse(const float* ctx, const float* motion, const float* bands, const float* window, int radius,
                                 double window_sum_sq, int64_t B, int T, int H, int W, int levels, int ar_order, float* phi, float* gamma,
@@ -267,8 +267,8 @@ extern "C" int pd_anvil_analyse(const float* ctx, const float* motion, const flo
                    (const void*)gamma != (const void*)motion,
                "pd_anvil_analyse: an output aliases an input");
   static bool lds_spectra[PD_MAX_DEVICES], lds_cascade[PD_MAX_DEVICES];
-  if (int rc = st_raise_lds("pd_anvil_analyse", (const void*)anvil_spectra_kernel, lds_spectra)) return rc;
-  if (int rc = st_raise_lds("pd_anvil_analyse", (const void*)anvil_cascade_kernel, lds_cascade)) return rc;
+  if (int rc = pd_raise_lds("pd_anvil_analyse", (const void*)anvil_spectra_kernel, ST_LDS_LIMIT, lds_spectra)) return rc;
+  if (int rc = pd_raise_lds("pd_anvil_analyse", (const void*)anvil_cascade_kernel, ST_LDS_LIMIT, lds_cascade)) return rc;
   char* w = (char*)ws;
   hipLaunchKernelGGL(anvil_spectra_kernel, dim3(2, (unsigned)B), dim3(ST_THREADS), st_frame_lds(H, W), (hipStream_t)stream, ctx, motion, T, H,
                      W, ar_order, (float2*)(w + g.z), (double*)(w + g.ms));

@@ -649,15 +649,7 @@ static int launch_attn_block(const pd_attn_block_args_k& a, hipStream_t s) {
   static_assert(epi <= work, "the epilogue slab must not reach the bias / token tables");
   static_assert((NS == 3 ? 2 : 1) * lds <= 160 * 1024, "two workgroups per CU (one with the deep ring)");
   static bool attr_set_dev[PD_MAX_DEVICES];
-  bool& attr_set = attr_set_dev[pd_cur_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_block_kernel<C, KT, RPC, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      pd_set_error("pd_attn_block_fused: hipFuncSetAttribute(%d) failed: %s", lds, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (int rc = pd_raise_lds("pd_attn_block_fused", (const void*)attn_block_kernel<C, KT, RPC, NS>, lds, attr_set_dev)) return rc;
   const int64_t cuboids = (int64_t)a.B * a.nc;
   constexpr int CPW = 64 / RPC;
   hipLaunchKernelGGL((attn_block_kernel<C, KT, RPC, NS>), dim3((unsigned)((cuboids + CPW - 1) / CPW)), dim3(512), lds, s, a);

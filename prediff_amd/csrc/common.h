@@ -57,6 +57,19 @@ static inline int pd_cur_device() {
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= PD_MAX_DEVICES) d = 0;
   return d;
 }
+// raise the dynamic-LDS limit of kernel `fn` to `bytes` once per device; done_per_device: the launcher's own static bool[PD_MAX_DEVICES]
+static inline int pd_raise_lds(const char* who, const void* fn, int bytes, bool* done_per_device) {
+  bool& set = done_per_device[pd_cur_device()];
+  if (!set) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+      pd_set_error("%s: hipFuncSetAttribute(%d) failed: %s", who, bytes, hipGetErrorString(e));
+      return PD_ERR_LAUNCH;
+    }
+    set = true;
+  }
+  return PD_OK;
+}
 
 // compute units of the current device (MI355X: 256), asked once per device: grid sizes and form heuristics derive from it
 static inline int pd_num_cus() {
@@ -201,6 +214,11 @@ __device__ __forceinline__ float act_apply(float v, int act) {
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

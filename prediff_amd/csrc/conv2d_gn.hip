@@ -251,15 +251,7 @@ static int launch_conv2d_gn(const float* x, const float* stats, const float* gam
   constexpr int lds_epi = 4 * 64 * 64 * 4;
   constexpr int lds = lds_main > lds_epi ? lds_main : lds_epi;
   static bool attr_set_dev[PD_MAX_DEVICES];
-  bool& attr_set = attr_set_dev[pd_cur_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv2d_gn_kernel<UP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      pd_set_error("pd_conv2d_gn_silu: hipFuncSetAttribute(%d) failed: %s", lds, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (int rc = pd_raise_lds("pd_conv2d_gn_silu", (const void*)conv2d_gn_kernel<UP>, lds, attr_set_dev)) return rc;
   const int64_t grid = (int64_t)N * (H / 8) * (Wd / 16) * (Cout / 128);
   PD_CHECK_ARG(grid < (1ll << 31), "pd_conv2d_gn_silu: grid too large");
   hipLaunchKernelGGL(conv2d_gn_kernel<UP>, dim3((unsigned)grid), dim3(256), lds, stream, a);

@@ -404,15 +404,7 @@ template <int L, bool BORDER>
 static int launch_halo(const pd_igemm_args& a, hipStream_t s) {
   constexpr int LDS = Lay<L>::LDS;
   static bool attr_set_dev[PD_MAX_DEVICES];
-  bool& attr_set = attr_set_dev[pd_cur_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3d_halo_kernel<L, BORDER>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      pd_set_error("pd_igemm: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (int rc = pd_raise_lds("pd_igemm", (const void*)conv3d_halo_kernel<L, BORDER>, LDS, attr_set_dev)) return rc;
   const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
   hipLaunchKernelGGL((conv3d_halo_kernel<L, BORDER>), dim3(tiles, 1, 1), dim3(512), LDS, s, a);
   PD_CHECK_LAUNCH();

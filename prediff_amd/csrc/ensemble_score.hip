@@ -15,6 +15,7 @@
 // G = 256 / P threads; the pairwise term is M (M - 1) / 2 LDS differences per pixel.  The floating sums are reduced deterministically:
 // fixed-order per-pixel and per-block trees, per-block partials in a workspace, and a fixed-order final pass per (t, sum) -- no float
 // atomics, so the same inputs give the same bits.  Integer counters use int64 atomics (order independent).
+#include "axes.h"
 #include "common.h"
 
 namespace {
@@ -24,16 +25,12 @@ constexpr int ES_MAXM = 512;           // members (8 GPUs x 64)
 constexpr int ES_TILE_FLOATS = 8192;   // LDS member tile: P * M floats (32 KB)
 constexpr int ES_THREADS = 256;
 
-struct Geom {
-  int64_t n, t, ho, wo, c;   // pooled sizes (ho = H / s, wo = W / s)
+struct Geom : Axes5 {        // pooled sizes: h = H / s, w = W / s
   int s;
-};
-struct Strides {
-  int64_t n, t, h, w, c;
 };
 
 // the pooled value of cell (ho, wo) of the (n, t, c) plane at `base`: max over the s x s window, NaN if any element is NaN
-__device__ __forceinline__ float pooled(const float* __restrict__ base, const Strides& st, int64_t ho, int64_t wo, int s, float divisor) {
+__device__ __forceinline__ float pooled(const float* __restrict__ base, const Axes5& st, int64_t ho, int64_t wo, int s, float divisor) {
   float m = -INFINITY;
   bool nan = false;
   for (int dh = 0; dh < s; ++dh) {
@@ -51,20 +48,20 @@ __device__ __forceinline__ float pooled(const float* __restrict__ base, const St
 // grid (chunks, slabs): a block stays inside one (n, t) slab of ho * wo * c cells and walks the slabs with a grid stride.
 __global__ void __launch_bounds__(256) sevir_skill_pooled_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                                  const float* __restrict__ thr, int nthr, float divisor,
-                                                                 long long* __restrict__ counts, Geom g, Strides sp, Strides stt,
+                                                                 long long* __restrict__ counts, Geom g, Axes5 sp, Axes5 stt,
                                                                  int keep_seq) {
   float th[ES_MAXTHR];
 #pragma unroll
   for (int k = 0; k < ES_MAXTHR; ++k) th[k] = k < nthr ? thr[k] : 3.0e38f;
   const int lane = threadIdx.x & 63;
-  const int64_t nslab = g.n * g.t, ncell = g.ho * g.wo * g.c;
+  const int64_t nslab = g.n * g.t, ncell = g.h * g.w * g.c;
   for (int64_t slab = blockIdx.y; slab < nslab; slab += gridDim.y) {
     const int64_t n = slab / g.t, t = slab % g.t;
     int h[ES_MAXTHR], ms[ES_MAXTHR], fa[ES_MAXTHR];
 #pragma unroll
     for (int k = 0; k < ES_MAXTHR; ++k) h[k] = ms[k] = fa[k] = 0;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < ncell; q += (int64_t)gridDim.x * 256) {
-      const int64_t c = q % g.c, wo = (q / g.c) % g.wo, ho = q / (g.c * g.wo);
+      const int64_t c = q % g.c, wo = (q / g.c) % g.w, ho = q / (g.c * g.w);
       const float pv = pooled(pred + n * sp.n + t * sp.t + c * sp.c, sp, ho, wo, g.s, divisor);
       const float tv = pooled(target + n * stt.n + t * stt.t + c * stt.c, stt, ho, wo, g.s, divisor);
       const bool ok = !(isnan(pv) || isnan(tv));
@@ -99,7 +96,7 @@ __global__ void __launch_bounds__(256) sevir_skill_pooled_kernel(const float* __
 // ws[b * 4 + k]: the block's fp64 partial of sum k.
 __global__ void __launch_bounds__(ES_THREADS) ensemble_score_kernel(const float* __restrict__ ens, const float* __restrict__ target,
                                                                     const float* __restrict__ thr, int nthr, float divisor, int M,
-                                                                    int64_t ens_stride_m, Geom g, Strides se, Strides stt, int P,
+                                                                    int64_t ens_stride_m, Geom g, Axes5 se, Axes5 stt, int P,
                                                                     int64_t tiles, int keep_seq, long long* __restrict__ n_valid,
                                                                     long long* __restrict__ brier, double* __restrict__ ws) {
   extern __shared__ float xs[];                      // [M][P] member values of the tile
@@ -116,7 +113,7 @@ __global__ void __launch_bounds__(ES_THREADS) ensemble_score_kernel(const float*
   const int64_t b = blockIdx.x;
   const int64_t slab = b / tiles, tile = b % tiles;
   const int64_t n = slab / g.t, t = slab % g.t;
-  const int64_t ncell = g.ho * g.wo * g.c, cell0 = tile * P;
+  const int64_t ncell = g.h * g.w * g.c, cell0 = tile * P;
 
   float th[ES_MAXTHR];
 #pragma unroll
@@ -140,8 +137,8 @@ __global__ void __launch_bounds__(ES_THREADS) ensemble_score_kernel(const float*
     float mx = -INFINITY;
     int nan = 0;
     if (act) {
-      const int64_t c = q % g.c, wo = (q / g.c) % g.wo, ho = q / (g.c * g.wo);
-      const Strides& st = m < M ? se : stt;
+      const int64_t c = q % g.c, wo = (q / g.c) % g.w, ho = q / (g.c * g.w);
+      const Axes5& st = m < M ? se : stt;
       const float* src = m < M ? ens + m * ens_stride_m + n * se.n + t * se.t + c * se.c : target + n * stt.n + t * stt.t + c * stt.c;
       for (int dh = 0; dh < g.s; ++dh) {
         const float* row = src + (ho * g.s + dh) * st.h + wo * g.s * st.w;
@@ -298,19 +295,12 @@ __global__ void __launch_bounds__(256) ensemble_score_final_kernel(const double*
 }
 
 bool read_geom(const int64_t* sizes, int s, Geom& g) {
-  if (!sizes || s < 1) return false;
-  for (int i = 0; i < 5; ++i)
-    if (sizes[i] < 1) return false;
-  g.n = sizes[0];
-  g.t = sizes[1];
-  g.ho = sizes[2] / s;
-  g.wo = sizes[3] / s;
-  g.c = sizes[4];
+  if (s < 1 || !read_axes(sizes, g)) return false;
+  g.h /= s;
+  g.w /= s;
   g.s = s;
   return true;
 }
-
-Strides read_strides(const int64_t* st) { return Strides{st[0], st[1], st[2], st[3], st[4]}; }
 
 // pixels per block: the largest power of two with P * M <= ES_TILE_FLOATS, halved (down to 1) while the update gives fewer than 1024
 // blocks (pooled frames, one context) -- more threads per pixel and more blocks reading the windows instead of idle CUs
@@ -329,7 +319,7 @@ extern "C" int pd_sevir_skill_counts_pooled(const float* pred, const float* targ
   PD_CHECK_ARG(pred && target && thresholds && counts && pred_strides && target_strides, "pd_sevir_skill_counts_pooled: null pointer");
   Geom g;
   PD_CHECK_ARG(read_geom(sizes, pool, g) && nthr > 0 && nthr <= ES_MAXTHR, "pd_sevir_skill_counts_pooled: bad sizes / pool / thresholds");
-  const int64_t ncell = g.ho * g.wo * g.c, nslab = g.n * g.t;
+  const int64_t ncell = g.h * g.w * g.c, nslab = g.n * g.t;
   PD_CHECK_ARG(ncell * nslab < (1ll << 40), "pd_sevir_skill_counts_pooled: more than 2^40 cells in one update");
   if (ncell == 0) return PD_OK;                     // a pool larger than the frame: no cell, nothing counted
   const unsigned chunks = (unsigned)std::min((int64_t)64, (ncell + 255) / 256);
@@ -343,7 +333,7 @@ extern "C" int pd_sevir_skill_counts_pooled(const float* pred, const float* targ
 extern "C" int64_t pd_ensemble_score_ws_doubles(int M, const int64_t* sizes, int pool) {
   Geom g;
   if (M < 1 || M > ES_MAXM || !read_geom(sizes, pool, g)) return -1;
-  const int64_t ncell = g.ho * g.wo * g.c, P = tile_pixels(M, g.n * g.t, ncell);
+  const int64_t ncell = g.h * g.w * g.c, P = tile_pixels(M, g.n * g.t, ncell);
   return std::max<int64_t>(1, g.n * g.t * ((ncell + P - 1) / P) * 4);
 }
 
@@ -356,7 +346,7 @@ extern "C" int pd_ensemble_score_update(const float* ens, const float* target, c
   PD_CHECK_ARG(M >= 1 && M <= ES_MAXM, "pd_ensemble_score_update: %d members (supported: 1 .. %d)", M, ES_MAXM);
   Geom g;
   PD_CHECK_ARG(read_geom(sizes, pool, g) && nthr > 0 && nthr <= ES_MAXTHR, "pd_ensemble_score_update: bad sizes / pool / thresholds");
-  const int64_t ncell = g.ho * g.wo * g.c;
+  const int64_t ncell = g.h * g.w * g.c;
   const int P = tile_pixels(M, g.n * g.t, ncell);
   const int64_t tiles = (ncell + P - 1) / P, nblocks = g.n * g.t * tiles;
   PD_CHECK_ARG(ws_doubles >= nblocks * 4, "pd_ensemble_score_update: workspace of %lld doubles < %lld", (long long)ws_doubles,

@@ -24,6 +24,7 @@
 // Bank conflicts: consecutive lanes read consecutive columns everywhere (staging, products, both box passes): conflict-free.
 // Every index is formed from clamped integers or from a float clamped to the frame first (a NaN clamps to 0): garbage in the context gives
 // garbage motion, never an address outside the buffers.
+#include "bilinear.h"
 #include "common.h"
 
 namespace {
@@ -35,7 +36,6 @@ constexpr int LK_RSTEP = LK_THREADS / LK_TILE;                 // rows a pass of
 constexpr int LK_HSUMS = 8;                                    // row sums a thread holds: 5 (32 + 2 R) <= 8 LK_RSTEP
 constexpr int LK_CELLS = 3, LK_BATCH = 3, LK_STAGE = 3;        // region / staged cells of a thread: (32 + 2 R)^2, (34 + 2 R)^2 <= 3 LK_THREADS
 constexpr int LK_MAX_SIDE = 512, LK_MIN_COARSE = 4, LK_MAX_LEVELS = 8, LK_MAX_PAIRS = 16, LK_MAX_ITERS = 64;
-constexpr float ADV_FAR = 1048576.f;                           // 2^20
 constexpr int LK_MAX_RW = LK_TILE + 2 * LK_MAX_RADIUS;
 static_assert(LK_MAX_RW * LK_MAX_RW <= LK_CELLS * LK_THREADS && (LK_MAX_RW + 2) * (LK_MAX_RW + 2) <= LK_STAGE * LK_THREADS &&
               5 * LK_MAX_RW <= LK_HSUMS * LK_RSTEP && LK_CELLS % LK_BATCH == 0 && LK_TILE % LK_RSTEP == 0,
@@ -245,9 +245,8 @@ __global__ void __launch_bounds__(LK_THREADS) lk_iter_kernel(const float* __rest
   }
 }
 
-// F_k(y, x) = bil_fill(frame, y - k v_y, x - k v_x), k = 1 .. K: one thread per (b, y, x), x fastest, so that each of its K stores is
-// coalesced along W.  A tap outside the frame reads `fill`; a coordinate that is not finite or lies further than 2^20 from the frame
-// gives `fill` before any integer is made of it (the motion may be the caller's).
+// F_k(y, x) = bil_fill(frame, y - k v_y, x - k v_x) (bilinear.h), k = 1 .. K: one thread per (b, y, x), x fastest, so that each of its K
+// stores is coalesced along W.
 __global__ void __launch_bounds__(256) advect_kernel(const float* __restrict__ frame, int64_t frame_stride, const float* __restrict__ motion,
                                                      float* __restrict__ out, int K, int H, int W, int64_t total, float fill) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -261,24 +260,7 @@ __global__ void __launch_bounds__(256) advect_kernel(const float* __restrict__ f
   float* o = out + b * K * (int64_t)HW + yx;
 #pragma unroll 4
   for (int k = 1; k <= K; ++k, o += HW) {
-    const float cy = (float)y - (float)k * vy, cx = (float)x - (float)k * vx;
-    float r = fill;
-    // false for a NaN
-    if (cy >= -ADV_FAR && cy <= (float)(H - 1) + ADV_FAR && cx >= -ADV_FAR && cx <= (float)(W - 1) + ADV_FAR) {
-      const float y0f = floorf(cy), x0f = floorf(cx);
-      const float fy = cy - y0f, fx = cx - x0f;
-      const int y0 = (int)y0f, x0 = (int)x0f;
-      const bool r0 = y0 >= 0 && y0 < H, r1 = y0 + 1 >= 0 && y0 + 1 < H;
-      const bool c0 = x0 >= 0 && x0 < W, c1 = x0 + 1 >= 0 && x0 + 1 < W;
-      const float i00 = r0 && c0 ? I[y0 * W + x0] : fill;
-      const float i01 = r0 && c1 ? I[y0 * W + x0 + 1] : fill;
-      const float i10 = r1 && c0 ? I[(y0 + 1) * W + x0] : fill;
-      const float i11 = r1 && c1 ? I[(y0 + 1) * W + x0 + 1] : fill;
-      const float top = i00 + fx * (i01 - i00);
-      const float bot = i10 + fx * (i11 - i10);
-      r = top + fy * (bot - top);
-    }
-    *o = r;
+    *o = bil_fill(I, H, W, (float)y - (float)k * vy, (float)x - (float)k * vx, fill);
   }
 }
 
@@ -320,15 +302,7 @@ extern "C" int pd_lk_motion(const float* ctx, float* motion, int64_t B, int T, i
   const int lds = ((RW + 2) * (RW + 2) + 5 * RW * RW) * 4;
   if (lds > 48 * 1024) {
     static bool attr_set_dev[PD_MAX_DEVICES];
-    bool& attr_set = attr_set_dev[pd_cur_device()];
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)lk_iter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      if (e != hipSuccess) {
-        pd_set_error("pd_lk_motion: hipFuncSetAttribute(%d) failed: %s", 64 * 1024, hipGetErrorString(e));
-        return PD_ERR_LAUNCH;
-      }
-      attr_set = true;
-    }
+    if (int rc = pd_raise_lds("pd_lk_motion", (const void*)lk_iter_kernel, 64 * 1024, attr_set_dev)) return rc;
   }
   const float* prev = w;                                       // never read in the first launch (LK_FLOW_ZERO)
   for (int l = levels - 1; l >= 0; --l) {

@@ -476,19 +476,16 @@ __global__ void __launch_bounds__(512, NS == 2 ? 4 : 2) ffn64_kernel(const pd_ff
 #endif
 }
 
+// The launch's LDS grows with the hidden width (b1 is staged whole), so the limit is raised once to what the widest supported one needs:
+// the limit only admits a launch, the bytes a launch asks for (and with them its occupancy) are its own.
+constexpr int FFN_MAX_HD = 3072;
+
 template <int ACT, int NS = 2>
 static int launch_ffn64(const pd_ffn_args_k& a, hipStream_t s) {
-  const int bytes = NS * 32768 + 64 * 64 * 2 + a.Hd * 4;         // the weight slots (the epilogue slab re-uses them) + H tile + b1
-  static int attr_set_dev[PD_MAX_DEVICES];
-  int& attr_set = attr_set_dev[pd_cur_device()];
-  if (attr_set < bytes) {
-    hipError_t e = hipFuncSetAttribute((const void*)ffn64_kernel<ACT, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-      pd_set_error("pd_ffn_fused: hipFuncSetAttribute(%d) failed: %s", bytes, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = bytes;
-  }
+  constexpr int fixed = NS * 32768 + 64 * 64 * 2;                // the weight slots (the epilogue slab re-uses them) + H tile
+  const int bytes = fixed + a.Hd * 4;                            // + b1
+  static bool attr_set_dev[PD_MAX_DEVICES];
+  if (int rc = pd_raise_lds("pd_ffn_fused", (const void*)ffn64_kernel<ACT, NS>, fixed + FFN_MAX_HD * 4, attr_set_dev)) return rc;
   hipLaunchKernelGGL((ffn64_kernel<ACT, NS>), dim3((a.M + 63) / 64), dim3(512), bytes, s, a);
   PD_CHECK_LAUNCH();
   return PD_OK;
@@ -496,19 +493,13 @@ static int launch_ffn64(const pd_ffn_args_k& a, hipStream_t s) {
 
 template <int C, int ACT>
 static int launch_ffn(const pd_ffn_args_k& a, hipStream_t s) {
-  const int lds = 128 * C * 2 + 128 * 64 * 2 + 64 * C * 2 + C * 64 * 2 + a.Hd * 4;
+  constexpr int tiles = 128 * C * 2 + 128 * 64 * 2 + 64 * C * 2 + C * 64 * 2;
   constexpr int epi = 8 * 32 * (C / 2) * 4;
+  const int lds = tiles + a.Hd * 4;
   const int bytes = lds > epi ? lds : epi;
-  static int attr_set_dev[PD_MAX_DEVICES];
-  int& attr_set = attr_set_dev[pd_cur_device()];
-  if (attr_set < bytes) {
-    hipError_t e = hipFuncSetAttribute((const void*)ffn_fused_kernel<C, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-      pd_set_error("pd_ffn_fused: hipFuncSetAttribute(%d) failed: %s", bytes, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = bytes;
-  }
+  static_assert(tiles + FFN_MAX_HD * 4 >= epi && tiles + FFN_MAX_HD * 4 <= 160 * 1024, "the raised limit covers every supported launch");
+  static bool attr_set_dev[PD_MAX_DEVICES];
+  if (int rc = pd_raise_lds("pd_ffn_fused", (const void*)ffn_fused_kernel<C, ACT>, tiles + FFN_MAX_HD * 4, attr_set_dev)) return rc;
   hipLaunchKernelGGL((ffn_fused_kernel<C, ACT>), dim3((a.M + 127) / 128), dim3(512), bytes, s, a);
   PD_CHECK_LAUNCH();
   return PD_OK;
@@ -516,7 +507,7 @@ static int launch_ffn(const pd_ffn_args_k& a, hipStream_t s) {
 
 #if !PD_IS_F16
 extern "C" int pd_ffn_fused_supported(int C, int Hd) {
-  return (C == 64 || C == 128 || C == 256) && Hd > 0 && Hd % 64 == 0 && Hd <= 3072;   // LDS: 144 KB tiles + 4*Hd bytes of bias
+  return (C == 64 || C == 128 || C == 256) && Hd > 0 && Hd % 64 == 0 && Hd <= FFN_MAX_HD;  // LDS: 144 KB tiles + 4*Hd bytes of bias
 }
 extern "C" int pd_f16_ffn_fused(const float*, float*, const float*, const float*, const pd_bf16*, const float*, const pd_bf16*, const float*, int64_t, int,
                                 int, int, float, const pd_call_opts*, pd_stream_t);

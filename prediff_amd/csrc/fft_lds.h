@@ -8,6 +8,14 @@
 namespace {
 
 constexpr int SP_PER_THREAD = 16;                              // complex elements a thread holds during one stage
+constexpr int SP_MIN_SIDE = 8, SP_MAX_SIDE = 512;              // frame sides of the 2-D users (host check: sp_side_ok)
+
+// a side the 2-D transforms take: 2^a or 3 2^a within the limits
+inline bool sp_side_ok(int64_t n) {
+  if (n < SP_MIN_SIDE || n > SP_MAX_SIDE) return false;
+  if (n % 3 == 0) n /= 3;
+  return (n & (n - 1)) == 0;
+}
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }

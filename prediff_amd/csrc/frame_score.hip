@@ -21,6 +21,7 @@
 // triple per (member, tile) in the workspace, a fixed-order final pass per (step, sum) -- no floating-point atomics, the same inputs
 // give the same bits.  data_range R is a host float, or max(range_buf[0], range_buf[1]) read on the device after frame_range_kernel
 // has filled range_buf with max - min of pred and of target (torchmetrics' data_range=None); no value travels through the host.
+#include "axes.h"
 #include "common.h"
 
 namespace {
@@ -39,22 +40,12 @@ __device__ const double FS_G[FS_TAPS] = {0.0010283800844791092, 0.00759875813523
                                          0.2130055377112537,    0.26601172486179436,  0.2130055377112537,  0.10936068950970002,
                                          0.03600077212843083,   0.007598758135239185, 0.0010283800844791092};
 
-struct FsGeom {
-  int64_t n, t, h, w, c;
+struct FsGeom : Axes5 {
   int ty, tx;                 // tiles per plane
 };
-struct FsStrides {
-  int64_t n, t, h, w, c;
-};
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the 26 x 42 pixels at (r0, c0) of the plane at `src` -> dst (zero outside the frame: those feed no window that is counted)
-__device__ __forceinline__ void stage_tile(const float* __restrict__ src, const FsStrides& s, const FsGeom& g, int r0, int c0,
+__device__ __forceinline__ void stage_tile(const float* __restrict__ src, const Axes5& s, const FsGeom& g, int r0, int c0,
                                            float* __restrict__ dst) {
   for (int i = threadIdx.x; i < FS_IH * FS_IW; i += FS_THREADS) {
     const int lr = i / FS_IW, lc = i % FS_IW;
@@ -119,7 +110,7 @@ __device__ __forceinline__ void vertical(const double* __restrict__ hs, int q, d
 // grid (planes * tiles, member chunks): block x = ((n T + t) C + c) tiles + tile scores members [y mchunk, (y + 1) mchunk) of its tile.
 // ws[(m nwg + x) 3 + k]: sum d^2, sum |d| over the pixels the tile owns, and the sum of ssim over its window positions.
 __global__ void __launch_bounds__(FS_THREADS) frame_score_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                                 FsGeom g, int64_t pred_stride_m, FsStrides sp, FsStrides st, int M,
+                                                                 FsGeom g, int64_t pred_stride_m, Axes5 sp, Axes5 st, int M,
                                                                  int mchunk, float data_range, const float* __restrict__ range_buf,
                                                                  double* __restrict__ ws) {
   __shared__ float ps[FS_IH * FS_IWS], ts[FS_IH * FS_IWS];
@@ -239,7 +230,7 @@ __global__ void __launch_bounds__(256) frame_score_final_kernel(const double* __
 // min / max of pred (M members) and of target.  A wave takes one (member | target, n, t, c, h) row at a time, its lanes the W axis.
 // part[block][5]: min p, max p, min t, max t, NaN flags (bit 0: pred, bit 1: target).
 __global__ void __launch_bounds__(256) frame_range_kernel(const float* __restrict__ pred, const float* __restrict__ target, FsGeom g,
-                                                          int64_t pred_stride_m, FsStrides sp, FsStrides st, int M,
+                                                          int64_t pred_stride_m, Axes5 sp, Axes5 st, int M,
                                                           double* __restrict__ part) {
   __shared__ float red[4][4];
   __shared__ int nred[4];
@@ -251,7 +242,7 @@ __global__ void __launch_bounds__(256) frame_range_kernel(const float* __restric
     const int64_t m = row / rows, q = row % rows;
     const int64_t h = q % g.h, c = (q / g.h) % g.c, t = (q / (g.h * g.c)) % g.t, n = q / (g.h * g.c * g.t);
     const bool is_t = m == M;
-    const FsStrides& s = is_t ? st : sp;
+    const Axes5& s = is_t ? st : sp;
     const float* src = is_t ? target + n * st.n + t * st.t + c * st.c + h * st.h
                             : pred + m * pred_stride_m + n * sp.n + t * sp.t + c * sp.c + h * sp.h;
     float lo = INFINITY, hi = -INFINITY;
@@ -316,10 +307,7 @@ __global__ void __launch_bounds__(FS_RANGE_BLOCKS) frame_range_final_kernel(cons
 }
 
 bool fs_geom(const int64_t* sizes, FsGeom& g) {
-  if (!sizes) return false;
-  for (int i = 0; i < 5; ++i)
-    if (sizes[i] < 1) return false;
-  g.n = sizes[0], g.t = sizes[1], g.h = sizes[2], g.w = sizes[3], g.c = sizes[4];
+  if (!read_axes(sizes, g)) return false;
   if (g.h < FS_TAPS || g.w < FS_TAPS || g.h > (1 << 20) || g.w > (1 << 20)) return false;
   g.ty = (int)((g.h - FS_HALO + FS_TH - 1) / FS_TH);
   g.tx = (int)((g.w - FS_HALO + FS_TW - 1) / FS_TW);
@@ -332,8 +320,6 @@ int64_t fs_nwg(const FsGeom& g) {
   if (planes * g.ty * g.tx >= (double)(1 << 30) || planes * (double)g.h * (double)g.w >= (double)(1ll << 40)) return -1;
   return g.n * g.t * g.c * g.ty * g.tx;
 }
-
-FsStrides fs_strides(const int64_t* s) { return FsStrides{s[0], s[1], s[2], s[3], s[4]}; }
 
 }  // namespace
 
@@ -359,7 +345,7 @@ extern "C" int pd_frame_score_update(const float* pred, const float* target, int
   PD_CHECK_ARG(fs_geom(sizes, g) && need > 0, "pd_frame_score_update: too many frames / pixels in one update");
   PD_CHECK_ARG(ws_doubles >= need, "pd_frame_score_update: workspace of %lld doubles < %lld", (long long)ws_doubles, (long long)need);
   const int64_t nwg = fs_nwg(g);
-  const FsStrides sp = fs_strides(pred_strides + 1), st = fs_strides(target_strides);
+  const Axes5 sp = read_strides(pred_strides + 1), st = read_strides(target_strides);
   if (range_buf) {
     double* part = ws + nwg * M * 3;
     const int64_t rows = (int64_t)(M + 1) * g.n * g.t * g.c * g.h;

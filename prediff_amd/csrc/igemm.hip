@@ -243,16 +243,7 @@ static int launch_igemm(const pd_igemm_args& a, hipStream_t s) {
   constexpr int epi = 4 * (BM / 2) * (BN / 2) * 4 / ESLAB;
   constexpr int lds = NS * stage > epi ? NS * stage : epi;   // the accumulator slab of the epilogue re-uses the operand ring
   static bool attr_set_dev[PD_MAX_DEVICES];
-  bool& attr_set = attr_set_dev[pd_cur_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, NS, SPLIT, KIND, OCC, ESLAB>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      pd_set_error("pd_igemm: hipFuncSetAttribute(%d) failed: %s", lds, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (int rc = pd_raise_lds("pd_igemm", (const void*)igemm_kernel<BM, BN, BK, NS, SPLIT, KIND, OCC, ESLAB>, lds, attr_set_dev)) return rc;
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   dim3 grid(tiles, 1, a.nbatch > 0 ? a.nbatch : 1);
   hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, NS, SPLIT, KIND, OCC, ESLAB>), grid, dim3(256), lds, s, a);

@@ -647,15 +647,7 @@ template <int KIND, bool F8 = false, bool WF = false>
 static int launch256_splitk(const pd_igemm_args& a, hipStream_t s) {
   constexpr int lds = 2 * KBUF;
   static bool attr_set_dev[PD_MAX_DEVICES];
-  bool& attr_set = attr_set_dev[pd_cur_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)igemm256_kernel<KIND, 8, true, F8, false, true, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      pd_set_error("pd_igemm: hipFuncSetAttribute(%d) failed: %s", lds, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (int rc = pd_raise_lds("pd_igemm", (const void*)igemm256_kernel<KIND, 8, true, F8, false, true, WF>, lds, attr_set_dev)) return rc;
   const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
   hipLaunchKernelGGL((igemm256_kernel<KIND, 8, true, F8, false, true, WF>), dim3(tiles, a.ksplit, 1), dim3(512), lds, s, a);
   PD_CHECK_LAUNCH();
@@ -694,15 +686,7 @@ static int launch256(const pd_igemm_args& a, hipStream_t s) {
   constexpr int lds = 2 * KBUF;
   constexpr int BM = RT == 8 ? 256 : 16 * RT + 96;
   static bool attr_set_dev[PD_MAX_DEVICES];
-  bool& attr_set = attr_set_dev[pd_cur_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)igemm256_kernel<KIND, RT, false, F8, SP, P2, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      pd_set_error("pd_igemm: hipFuncSetAttribute(%d) failed: %s", lds, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (int rc = pd_raise_lds("pd_igemm", (const void*)igemm256_kernel<KIND, RT, false, F8, SP, P2, WF>, lds, attr_set_dev)) return rc;
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + 255) / 256);
   dim3 grid(tiles, 1, a.nbatch > 0 ? a.nbatch : 1);
   hipLaunchKernelGGL((igemm256_kernel<KIND, RT, false, F8, SP, P2, WF>), grid, dim3(512), lds, s, a);
@@ -744,15 +728,8 @@ template <int KIND, bool SK>
 static int launch256_mx(const pd_igemm_args& a, const MxK& mx, hipStream_t s) {
   constexpr int lds = 2 * KBUF + 2 * SBUF;
   static bool attr_set_dev[PD_MAX_DEVICES];
-  bool& attr_set = attr_set_dev[pd_cur_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)igemm256_kernel<KIND, 8, SK, true, false, true, false, true, MxK>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      pd_set_error("pd_igemm_mx: hipFuncSetAttribute(%d) failed: %s", lds, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (int rc = pd_raise_lds("pd_igemm_mx", (const void*)igemm256_kernel<KIND, 8, SK, true, false, true, false, true, MxK>, lds, attr_set_dev))
+    return rc;
   const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
   hipLaunchKernelGGL((igemm256_kernel<KIND, 8, SK, true, false, true, false, true, MxK>), dim3(tiles, SK ? a.ksplit : 1, 1), dim3(512), lds, s, a, mx);
   PD_CHECK_LAUNCH();

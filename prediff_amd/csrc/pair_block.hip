@@ -917,15 +917,7 @@ static int launch_pair(const pd_pair_args_k& a, hipStream_t s) {
   using namespace pairk;
   constexpr int LDS_BYTES = G<CW>::LDS_BYTES;
   static bool attr_set_dev[PD_MAX_DEVICES];
-  bool& attr_set = attr_set_dev[pd_cur_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)pair_kernel<NC, CW, NWV, MODE, WP, NSPL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) {
-      pd_set_error("pd_attn_ffn_pair: hipFuncSetAttribute(%d) failed: %s", LDS_BYTES, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (int rc = pd_raise_lds("pd_attn_ffn_pair", (const void*)pair_kernel<NC, CW, NWV, MODE, WP, NSPL>, LDS_BYTES, attr_set_dev)) return rc;
   // persistent: every workgroup takes the same number of tiles (the last few one less), one workgroup per CU
   // (split forms: PAIR_NSPL workgroups per tile -- blockIdx.y = the slice)
   const int ncu = pd_num_cus();

@@ -33,29 +33,17 @@
 // Radial reduce: deterministic, no atomics.  One wave per bin walks the bin's cells in list order (lane-strided fp64 accumulators, then a
 // fixed-order butterfly); per-pair partials [pair][3][nb] go to the workspace in fp64, and spectrum_fold_kernel adds them to the state
 // pair by pair in index order.  The same inputs give the same bits.  No NaN masking: a NaN pixel makes its pair's bins NaN.
+#include "axes.h"
 #include "common.h"
 #include "fft_lds.h"
 
 namespace {
 
 constexpr int SP_MAXM = 512;
-constexpr int SP_MIN_SIDE = 8, SP_MAX_SIDE = 512;
 constexpr int SP_LDS_ELEMS = 1024 * SP_PER_THREAD;             // 16384: elements of one workgroup's set of lines
 constexpr int SP_LDS_LIMIT = 160 * 1024 - 512;
 constexpr int64_t SP_WS_CAP = 256ll << 20;
 
-struct SpGeom {
-  int64_t n, t, h, w, c;
-};
-struct SpStrides {
-  int64_t n, t, h, w, c;
-};
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // The three sums of bin b of one pair, by one wave: out[0], out[nb], out[2 nb].  z: the pair's transform, row pitch `pitch` (LDS or memory).
 __device__ __forceinline__ void bin_partials(const float2* __restrict__ z, int pitch, int H, int W, const int* __restrict__ cell_order,
@@ -90,14 +78,14 @@ struct SpPair {
   const float *p, *t;
 };
 // pair index ((m N + n) T + t) C + c -> the two planes
-__device__ __forceinline__ SpPair pair_planes(const float* pred, const float* target, const SpGeom& g, int64_t pred_stride_m,
-                                              const SpStrides& sp, const SpStrides& st, int64_t pair) {
+__device__ __forceinline__ SpPair pair_planes(const float* pred, const float* target, const Axes5& g, int64_t pred_stride_m,
+                                              const Axes5& sp, const Axes5& st, int64_t pair) {
   const int64_t c = pair % g.c, t = (pair / g.c) % g.t, n = (pair / (g.c * g.t)) % g.n, m = pair / (g.c * g.t * g.n);
   return SpPair{pred + m * pred_stride_m + n * sp.n + t * sp.t + c * sp.c, target + n * st.n + t * st.t + c * st.c};
 }
 
 // rows [r0, r0 + nr) of the pair's two planes -> z[(r - r0) * pitch + w] = window * (p + i t)
-__device__ __forceinline__ void load_rows(const SpPair& pp, const SpStrides& sp, const SpStrides& st, int H, int W, int r0, int nr,
+__device__ __forceinline__ void load_rows(const SpPair& pp, const Axes5& sp, const Axes5& st, int H, int W, int r0, int nr,
                                           int window, float2* __restrict__ z, int pitch) {
   for (int i = threadIdx.x; i < nr * W; i += blockDim.x) {
     const int lr = i / W, w = i - lr * W;
@@ -112,8 +100,8 @@ __device__ __forceinline__ void load_rows(const SpPair& pp, const SpStrides& sp,
 }
 
 // LDS-resident form.  grid: the chunk's pairs; dynamic LDS: (H (W + 1) + max(H, W)) complex.
-__global__ void __launch_bounds__(1024) spectrum_lds_kernel(const float* __restrict__ pred, const float* __restrict__ target, SpGeom g,
-                                                            int64_t pred_stride_m, SpStrides sp, SpStrides st, int64_t pair0,
+__global__ void __launch_bounds__(1024) spectrum_lds_kernel(const float* __restrict__ pred, const float* __restrict__ target, Axes5 g,
+                                                            int64_t pred_stride_m, Axes5 sp, Axes5 st, int64_t pair0,
                                                             const int* __restrict__ cell_order, const int* __restrict__ bin_start,
                                                             int nb, int window, double* __restrict__ part) {
   extern __shared__ float2 sp_smem[];
@@ -131,8 +119,8 @@ __global__ void __launch_bounds__(1024) spectrum_lds_kernel(const float* __restr
 }
 
 // Strip form 1: row FFTs.  grid (pairs, row blocks of `rows`); zws[pair][h][w].
-__global__ void __launch_bounds__(1024) spectrum_rows_kernel(const float* __restrict__ pred, const float* __restrict__ target, SpGeom g,
-                                                             int64_t pred_stride_m, SpStrides sp, SpStrides st, int64_t pair0, int rows,
+__global__ void __launch_bounds__(1024) spectrum_rows_kernel(const float* __restrict__ pred, const float* __restrict__ target, Axes5 g,
+                                                             int64_t pred_stride_m, Axes5 sp, Axes5 st, int64_t pair0, int rows,
                                                              int window, float2* __restrict__ zws) {
   extern __shared__ float2 sp_smem[];
   const int H = (int)g.h, W = (int)g.w, pitch = W + 1;
@@ -196,50 +184,22 @@ __global__ void __launch_bounds__(256) spectrum_fold_kernel(const double* __rest
   if (b == 0 && k == 0) frames[tk] += cnt;
 }
 
-bool sp_side_ok(int64_t n) {
-  if (n < SP_MIN_SIDE || n > SP_MAX_SIDE) return false;
-  if (n % 3 == 0) n /= 3;
-  return (n & (n - 1)) == 0;
-}
-
-bool sp_geom(const int64_t* sizes, SpGeom& g) {
-  if (!sizes) return false;
-  for (int i = 0; i < 5; ++i)
-    if (sizes[i] < 1) return false;
-  g.n = sizes[0], g.t = sizes[1], g.h = sizes[2], g.w = sizes[3], g.c = sizes[4];
-  return sp_side_ok(g.h) && sp_side_ok(g.w);
-}
+bool sp_geom(const int64_t* sizes, Axes5& g) { return read_axes(sizes, g) && sp_side_ok(g.h) && sp_side_ok(g.w); }
 
 // pairs of the call; -1 when they do not fit a grid
-int64_t sp_pairs(int M, const SpGeom& g) {
+int64_t sp_pairs(int M, const Axes5& g) {
   const double p = (double)M * (double)g.n * (double)g.t * (double)g.c;
   return p >= (double)(1 << 30) ? -1 : (int64_t)M * g.n * g.t * g.c;
 }
 
-bool sp_strip(const SpGeom& g) { return g.h * g.w > SP_LDS_ELEMS; }
-int sp_nb(const SpGeom& g) { return (int)(std::max(g.h, g.w) / 2 + 1); }
-int64_t sp_pair_bytes(const SpGeom& g) { return 3ll * sp_nb(g) * 8 + (sp_strip(g) ? g.h * g.w * 8 : 0); }
-
-SpStrides sp_strides(const int64_t* s) { return SpStrides{s[0], s[1], s[2], s[3], s[4]}; }
-
-// raise the dynamic-LDS limit of `fn` once per device
-int sp_raise_lds(const void* fn, bool* done) {
-  bool& set = done[pd_cur_device()];
-  if (!set) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS_LIMIT);
-    if (e != hipSuccess) {
-      pd_set_error("pd_spectrum_update: hipFuncSetAttribute(%d) failed: %s", SP_LDS_LIMIT, hipGetErrorString(e));
-      return PD_ERR_LAUNCH;
-    }
-    set = true;
-  }
-  return PD_OK;
-}
+bool sp_strip(const Axes5& g) { return g.h * g.w > SP_LDS_ELEMS; }
+int sp_nb(const Axes5& g) { return (int)(std::max(g.h, g.w) / 2 + 1); }
+int64_t sp_pair_bytes(const Axes5& g) { return 3ll * sp_nb(g) * 8 + (sp_strip(g) ? g.h * g.w * 8 : 0); }
 
 }  // namespace
 
 extern "C" int64_t pd_spectrum_ws_bytes(int M, const int64_t* sizes) {
-  SpGeom g;
+  Axes5 g;
   if (M < 1 || M > SP_MAXM || !sp_geom(sizes, g)) return -1;
   const int64_t pairs = sp_pairs(M, g);
   if (pairs < 0) return -1;
@@ -258,7 +218,7 @@ extern "C" int pd_spectrum_update(const float* pred, const float* target, int M,
     PD_CHECK_ARG(sp_side_ok(sizes[i]), "pd_spectrum_update: side %lld of the %lld x %lld frames is not supported (2^a or 3 * 2^a, %d .. %d)",
                  (long long)sizes[i], (long long)sizes[2], (long long)sizes[3], SP_MIN_SIDE, SP_MAX_SIDE);
   PD_CHECK_ARG(window == 0 || window == 1, "pd_spectrum_update: window %d (0: none, 1: hann)", window);
-  SpGeom g;
+  Axes5 g;
   PD_CHECK_ARG(sp_geom(sizes, g), "pd_spectrum_update: bad sizes");
   const int64_t pairs = sp_pairs(M, g);
   PD_CHECK_ARG(pairs > 0, "pd_spectrum_update: too many frames in one update");
@@ -270,15 +230,15 @@ extern "C" int pd_spectrum_update(const float* pred, const float* target, int M,
   const int64_t chunk = std::min(pairs, ws_bytes / per);
   const int H = (int)g.h, W = (int)g.w;
   const bool strip = sp_strip(g);
-  const SpStrides sp = sp_strides(pred_strides + 1), st = sp_strides(target_strides);
+  const Axes5 sp = read_strides(pred_strides + 1), st = read_strides(target_strides);
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)ws;                          // [chunk][3][nb]
   float2* zws = (float2*)(part + chunk * 3 * nb);      // [chunk][H][W], strip form only
   static bool lds_set[3][PD_MAX_DEVICES];
   if (strip) {
-    if (int rc = sp_raise_lds((const void*)spectrum_rows_kernel, lds_set[1])) return rc;
-    if (int rc = sp_raise_lds((const void*)spectrum_cols_kernel, lds_set[2])) return rc;
-  } else if (int rc = sp_raise_lds((const void*)spectrum_lds_kernel, lds_set[0])) {
+    if (int rc = pd_raise_lds("pd_spectrum_update", (const void*)spectrum_rows_kernel, SP_LDS_LIMIT, lds_set[1])) return rc;
+    if (int rc = pd_raise_lds("pd_spectrum_update", (const void*)spectrum_cols_kernel, SP_LDS_LIMIT, lds_set[2])) return rc;
+  } else if (int rc = pd_raise_lds("pd_spectrum_update", (const void*)spectrum_lds_kernel, SP_LDS_LIMIT, lds_set[0])) {
     return rc;
   }
   for (int64_t p0 = 0; p0 < pairs; p0 += chunk) {

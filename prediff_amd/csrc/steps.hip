@@ -83,13 +83,13 @@ __global__ void __launch_bounds__(ST_THREADS) steps_analyse_kernel(const float* 
     if (kind == 0) {
       double s[2] = {0.0, 0.0};
       ST_PIXELS(const float a0 = fmaxf(seq[(T - 1) * HW + i], thr);
-                const float a1 = fmaxf(st_bil_fill(seq + (T - 2) * HW, H, W, (float)y - vy[i], (float)x - vx[i]), thr);
+                const float a1 = fmaxf(bil_fill(seq + (T - 2) * HW, H, W, (float)y - vy[i], (float)x - vx[i], 0.f), thr);
                 z[li] = make_float2(a0, a1); s[0] += (double)a0 * (double)a0; s[1] += (double)a1 * (double)a1;)
       block_sum<2>(s, red);
       ms0 = fmax(s[0] / (double)HW, 1e-30), ms1 = fmax(s[1] / (double)HW, 1e-30);
     } else if (kind == 1) {
       double s[1] = {0.0};
-      ST_PIXELS(const float a2 = fmaxf(st_bil_fill(seq + (T - 3) * HW, H, W, (float)y - 2.f * vy[i], (float)x - 2.f * vx[i]), thr);
+      ST_PIXELS(const float a2 = fmaxf(bil_fill(seq + (T - 3) * HW, H, W, (float)y - 2.f * vy[i], (float)x - 2.f * vx[i], 0.f), thr);
                 z[li] = make_float2(a2, 0.f); s[0] += (double)a2 * (double)a2;)
       block_sum<1>(s, red);
       ms2 = fmax(s[0] / (double)HW, 1e-30);
@@ -252,7 +252,7 @@ __global__ void __launch_bounds__(ST_THREADS) steps_finish_kernel(const float* _
   ST_PIXELS(float v = q[li]; if (v > thr) v += shift; q[li] = v > thr ? v : 0.f;)
   __syncthreads();
   float* __restrict__ o = out + (int64_t)blockIdx.x * HW;
-  ST_PIXELS(o[i] = st_bil_fill(q, H, W, (float)y - (float)k * vy[i], (float)x - (float)k * vx[i]);)
+  ST_PIXELS(o[i] = bil_fill(q, H, W, (float)y - (float)k * vy[i], (float)x - (float)k * vx[i], 0.f);)
 }
 
 struct StLayout {
@@ -283,7 +283,7 @@ extern "C" int64_t pd_steps_ws_bytes(int64_t B, int M, int H, int W, int levels,
   PD_CHECK_ARG(st_layout(B, M, H, W, levels, ar, g),                                                                                        \
                who ": unsupported shape or options (%lld sequences, %d members, frames %d x %d, levels=%d, ar_order=%d): sides 2^a or "     \
                    "3 * 2^a, %d .. %d, H W <= %d; 2 <= levels <= floor(log2(max(H, W))) - 1; ar_order 1 or 2; B <= %d, M <= %d",             \
-               (long long)(B), M, H, W, levels, ar, ST_MIN_SIDE, ST_MAX_SIDE, ST_MAX_ELEMS, ST_MAX_BATCH, ST_MAX_MEMBERS)
+               (long long)(B), M, H, W, levels, ar, SP_MIN_SIDE, SP_MAX_SIDE, ST_MAX_ELEMS, ST_MAX_BATCH, ST_MAX_MEMBERS)
 
 extern "C" int pd_steps_analyse(const float* ctx, const float* motion, const float* bands, int64_t B, int T, int H, int W, int levels,
                                 int ar_order, float threshold, float* mu, float* sigma, float* phi, float* gamma, void* ws, int64_t ws_bytes,
@@ -297,7 +297,7 @@ extern "C" int pd_steps_analyse(const float* ctx, const float* motion, const flo
                "pd_steps_analyse: the workspace holds %lld bytes (8-byte aligned), %lld are needed", (long long)ws_bytes,
                (long long)g.analyse_bytes);
   static bool lds_set[PD_MAX_DEVICES];
-  if (int rc = st_raise_lds("pd_steps_analyse", (const void*)steps_analyse_kernel, lds_set)) return rc;
+  if (int rc = pd_raise_lds("pd_steps_analyse", (const void*)steps_analyse_kernel, ST_LDS_LIMIT, lds_set)) return rc;
   char* w = (char*)ws;
   hipLaunchKernelGGL(steps_analyse_kernel, dim3((unsigned)B), dim3(ST_THREADS), st_frame_lds(H, W), (hipStream_t)stream, ctx, motion, bands,
                      T, H, W, levels, ar_order, threshold, mu, sigma, phi, gamma, (float*)(w + g.n), (float*)(w + g.p), (float2*)(w + g.z));
@@ -318,7 +318,7 @@ extern "C" int pd_steps_evolve(const float* noise, const float* bands, const flo
   PD_CHECK_ARG(ws_bytes >= g.bytes && ((uintptr_t)ws & 7) == 0,
                "pd_steps_evolve: the workspace holds %lld bytes (8-byte aligned), %lld are needed", (long long)ws_bytes, (long long)g.bytes);
   static bool lds_set[PD_MAX_DEVICES];
-  if (int rc = st_raise_lds("pd_steps_evolve", (const void*)steps_evolve_kernel, lds_set)) return rc;
+  if (int rc = pd_raise_lds("pd_steps_evolve", (const void*)steps_evolve_kernel, ST_LDS_LIMIT, lds_set)) return rc;
   char* w = (char*)ws;
   hipLaunchKernelGGL(steps_evolve_kernel, dim3((unsigned)M, (unsigned)B), dim3(ST_THREADS), st_frame_lds(H, W), (hipStream_t)stream, noise,
                      bands, mu, sigma, phi, K, H, W, levels, (const float*)(w + g.n), (const float*)(w + g.p), (float2*)(w + g.zn),
@@ -331,7 +331,7 @@ extern "C" int pd_steps_finish(const float* ctx, const float* motion, const floa
                                float threshold, int mask, int match, pd_stream_t stream) {
   PD_CHECK_ARG(ctx && motion && R && out, "pd_steps_finish: null pointer");
   PD_CHECK_ARG(st_frame_ok(H, W), "pd_steps_finish: frames of %d x %d are not supported (sides 2^a or 3 * 2^a, %d .. %d, H W <= %d)", H, W,
-               ST_MIN_SIDE, ST_MAX_SIDE, ST_MAX_ELEMS);
+               SP_MIN_SIDE, SP_MAX_SIDE, ST_MAX_ELEMS);
   PD_CHECK_ARG(M >= 1 && M <= ST_MAX_MEMBERS && B >= 1 && B <= ST_MAX_BATCH && K >= 1 && K <= ST_MAX_LEADS && T >= 1 && T <= (1 << 16),
                "pd_steps_finish: bad sizes (M=%d, B=%lld, T=%d, K=%d)", M, (long long)B, T, K);
   PD_CHECK_ARG((int64_t)M * B * K <= 0x7fffffff, "pd_steps_finish: %lld frames in one call", (long long)((int64_t)M * B * K));
@@ -341,7 +341,7 @@ extern "C" int pd_steps_finish(const float* ctx, const float* motion, const floa
   PD_CHECK_ARG((const void*)out != (const void*)R && (const void*)out != (const void*)ctx && (const void*)out != (const void*)motion,
                "pd_steps_finish: out aliases an input");
   static bool lds_set[PD_MAX_DEVICES];
-  if (int rc = st_raise_lds("pd_steps_finish", (const void*)steps_finish_kernel, lds_set)) return rc;
+  if (int rc = pd_raise_lds("pd_steps_finish", (const void*)steps_finish_kernel, ST_LDS_LIMIT, lds_set)) return rc;
   hipLaunchKernelGGL(steps_finish_kernel, dim3((unsigned)((int64_t)M * B * K)), dim3(ST_THREADS), sizeof(float) * (size_t)H * W + sizeof(double) * ST_RED,
                      (hipStream_t)stream, ctx, motion, R, out, (int)B, T, K, H, W, threshold, mask, match);
   PD_CHECK_LAUNCH();

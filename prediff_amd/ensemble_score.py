@@ -27,116 +27,59 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .sevir_skill import axes_of, parse_preprocess
+from .score_base import SEVIRScoreBase, parse_preprocess, thresholds_on
 
-MAX_MEMBERS = 512
 METRICS = ("crps", "crps_fair", "brier", "rmse", "spread")
 
 
-class SEVIREnsembleScore:
+class SEVIREnsembleScore(SEVIRScoreBase):
+    METRICS = METRICS
+    SEQ_LEN_ERROR = AssertionError   # as SEVIRSkillScore
+    STATE = (("n_valid", torch.int64, lambda self, Tk: (Tk,)),
+             ("brier_sums", torch.int64, lambda self, Tk: (len(self.threshold_list), Tk)),
+             ("sums", torch.float64, lambda self, Tk: (4, Tk)))      # sum |x - y|, sum_ij |x_i - x_j|, (m - y)^2, s^2
+
     def __init__(self, layout: str = "NHWT", mode: str = "0", seq_len: Optional[int] = None, preprocess_type: str = "sevir",
                  threshold_list: Sequence[int] = (16, 74, 133, 160, 181, 219),
                  metrics_list: Sequence[str] = METRICS, eps: float = 1e-4):
-        if mode not in ("0", "1", "2"):
-            raise NotImplementedError(f"mode {mode} not supported!")
-        if "N" not in layout or "T" not in layout or len(set(layout)) != len(layout) or set(layout) - set("NTHWC"):
-            raise ValueError(f"layout {layout!r}: distinct letters of N, T, H, W, C with N and T present")
-        bad = [m for m in metrics_list if m not in METRICS]
-        if bad:
-            raise ValueError(f"unknown metrics {bad}; supported: {METRICS}")
+        # eps: accepted for keyword parity with SEVIRSkillScore; no score here divides by a count that eps would guard
+        self.threshold_list, self.eps = tuple(threshold_list), eps
+        super().__init__(layout, mode, seq_len, metrics_list)
         if not 1 <= len(threshold_list) <= 8:
             raise ValueError("1 to 8 thresholds are supported")
         self.preprocess_type = preprocess_type
         self.pool_scale = parse_preprocess(preprocess_type, layout)
-        self.layout, self.mode, self.seq_len = layout, mode, seq_len
-        # eps: accepted for keyword parity with SEVIRSkillScore; no score here divides by a count that eps would guard
-        self.threshold_list, self.metrics_list, self.eps = tuple(threshold_list), tuple(metrics_list), eps
-        self.keep_seq_len_dim = mode in ("1", "2")
-        if self.keep_seq_len_dim:
-            assert isinstance(seq_len, int), "seq_len must be provided when we need to keep seq_len dim."
-        self.reset()
 
     def reset(self):
+        super().reset()
         self.num_members = None      # M of the updates so far
-        self.n_valid = None          # int64 [T']
-        self.brier_sums = None       # int64 [thr, T']
-        self.sums = None             # fp64 [4, T']: sum |x - y|, sum_ij |x_i - x_j|, (m - y)^2, s^2
         self._thr = None
-        self._ws = None
 
     def update(self, ens: torch.Tensor, target: torch.Tensor):
-        if ens.dim() != len(self.layout) + 1 or tuple(ens.shape[1:]) != tuple(target.shape):
-            raise ValueError(f"ens must be (M,) + target.shape with target in layout {self.layout!r}; got {tuple(ens.shape)} "
-                             f"and {tuple(target.shape)}")
-        M = ens.shape[0]
-        if not 1 <= M <= MAX_MEMBERS:
-            raise ValueError(f"{M} members: 1 .. {MAX_MEMBERS} are supported")
+        x, y, M, sizes, xs, ys = self._members(ens, target)
         if self.num_members is not None and M != self.num_members:
             raise ValueError(f"{M} members after updates with {self.num_members}: reset() first")
-        if not (ens.is_cuda and target.is_cuda):
-            raise L.PrediffHipError("SEVIREnsembleScore.update runs on the HIP device the members were decoded on")
-        T = target.shape[self.layout.find("T")]
-        if self.keep_seq_len_dim:
-            assert T == self.seq_len
         dev = ens.device
-        if self.n_valid is None:
-            self._alloc_state(dev)
-        elif self.n_valid.device != dev:         # a zero state that sync() made before this rank's first update
-            self.n_valid, self.brier_sums, self.sums = (t.to(dev) for t in (self.n_valid, self.brier_sums, self.sums))
-        if self._thr is None or self._thr.device != self.n_valid.device:
-            self._thr = torch.tensor(self.threshold_list, dtype=torch.float32, device=self.n_valid.device)
-        x, y = ens.detach().float(), target.detach().float()          # read in place through their strides
-        sizes, xs = axes_of(self.layout, x, lead=1)
-        _, ys = axes_of(self.layout, y)
-        need = L.ensemble_score_ws_doubles(M, sizes, self.pool_scale)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.float64, device=dev)
+        self._state_on(dev)
+        self._thr = thresholds_on(self._thr, self.threshold_list, dev)
+        ws = self._workspace(L.ensemble_score_ws_doubles(M, sizes, self.pool_scale), torch.float64, dev)
         divisor = float(np.float32(1.0 / 255.0))       # as SEVIRSkillScore
         with L.on_device(ens):
-            L.ensemble_score_update(x, y, self._thr, divisor, M, sizes, [x.stride(0)] + xs, ys, self.pool_scale, self.keep_seq_len_dim,
-                                    self.n_valid, self.brier_sums, self.sums, self._ws)
+            L.ensemble_score_update(x, y, self._thr, divisor, M, sizes, xs, ys, self.pool_scale, self.keep_seq_len_dim,
+                                    self.n_valid, self.brier_sums, self.sums, ws)
         self.num_members = M
 
-    def _alloc_state(self, dev):
-        Tk = self.seq_len if self.keep_seq_len_dim else 1
-        self.n_valid = torch.zeros(Tk, dtype=torch.int64, device=dev)
-        self.brier_sums = torch.zeros((len(self.threshold_list), Tk), dtype=torch.int64, device=dev)
-        self.sums = torch.zeros((4, Tk), dtype=torch.float64, device=dev)
-
-    def sync(self, group=None):
-        """All-reduce the state with SUM over the ranks of `group`; every rank must call it, including ranks that made no update
-        (they take part with a zero state).  Each context must have been updated on exactly one rank.  The member count is agreed
-        as well: ranks that made updates must have used the same M (ValueError on every rank otherwise)."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        if self.n_valid is not None:
-            dev = self.n_valid.device
-        elif dist.get_backend(group) == "nccl":
-            dev = torch.device("cuda", torch.cuda.current_device())
-        else:
-            dev = torch.device("cpu")
-        if self.n_valid is None:
-            self._alloc_state(dev)
+    def _sync_more(self, dist, group):
+        """The member count is agreed as well: ranks that made updates must have used the same M (ValueError on every rank otherwise)."""
         # [max M, -min M] over the ranks with updates (a rank without any contributes 0 and -2^40)
         m = self.num_members
-        mm = torch.tensor([m, -m] if m is not None else [0, -(1 << 40)], dtype=torch.int64, device=dev)
+        mm = torch.tensor([m, -m] if m is not None else [0, -(1 << 40)], dtype=torch.int64, device=self.n_valid.device)
         dist.all_reduce(mm, op=dist.ReduceOp.MAX, group=group)
-        for t in (self.n_valid, self.brier_sums, self.sums):
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
         hi, lo = int(mm[0]), -int(mm[1])
         if hi > 0 and hi != lo:
             raise ValueError(f"sync: ranks updated with different member counts ({lo} .. {hi})")
         if hi > 0:
             self.num_members = hi
-
-    def _finish(self, per_t):
-        """per_t: (T',) scores -> the mode's form (scalar for "0" and "2", (T,) array for "1")."""
-        if self.mode == "0":
-            return float(per_t[0])
-        if self.mode == "1":
-            return per_t
-        return float(np.mean(per_t))
 
     def compute(self):
         Tk = self.seq_len if self.keep_seq_len_dim else 1

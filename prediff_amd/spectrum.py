@@ -35,9 +35,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .sevir_skill import axes_of
+from .score_base import SEVIRScoreBase
 
-MAX_MEMBERS = 512
 METRICS = ("psd_pred", "psd_target", "coherence", "lsd")
 WINDOWS = ("none", "hann")
 # the workspace one update may hold (complex frames of the strip form + per-pair partials); more pairs than fit run in several chunks
@@ -72,35 +71,24 @@ def spectrum_bins(H: int, W: int):
     return bins, order.astype(np.int32), bin_start, cells
 
 
-class SEVIRSpectralScore:
+class SEVIRSpectralScore(SEVIRScoreBase):
+    METRICS = METRICS
+    LAYOUT_NEEDS_HW = "the transform runs over H and W"
+    STATE = (("sums", torch.float64, lambda self, Tk: (3, Tk, max(self.hw) // 2 + 1)),       # S_p, S_t, S_x
+             ("frames", torch.int64, lambda self, Tk: (Tk,)))                               # pairs added
+
     def __init__(self, layout: str = "NTHWC", mode: str = "0", seq_len: Optional[int] = None,
                  metrics_list: Sequence[str] = METRICS, window: str = "none"):
-        if mode not in ("0", "1", "2"):
-            raise NotImplementedError(f"mode {mode} not supported!")
-        if "N" not in layout or "T" not in layout or len(set(layout)) != len(layout) or set(layout) - set("NTHWC"):
-            raise ValueError(f"layout {layout!r}: distinct letters of N, T, H, W, C with N and T present")
-        if "H" not in layout or "W" not in layout:
-            raise ValueError(f"layout {layout!r}: the transform runs over H and W, both must be named")
-        bad = [m for m in metrics_list if m not in METRICS]
-        if bad:
-            raise ValueError(f"unknown metrics {bad}; supported: {METRICS}")
         if window not in WINDOWS:
             raise ValueError(f"unknown window {window!r}; supported: {WINDOWS}")
-        self.layout, self.mode, self.seq_len = layout, mode, seq_len
-        self.metrics_list = tuple(metrics_list)
         self.window = window
-        self.keep_seq_len_dim = mode in ("1", "2")
-        if self.keep_seq_len_dim and not isinstance(seq_len, int):
-            raise ValueError("seq_len must be provided when we need to keep seq_len dim.")
         self._bins = {}              # (H, W, device) -> (cell_order, bin_start) int32 on the device
-        self.reset()
+        super().__init__(layout, mode, seq_len, metrics_list)
 
     def reset(self):
-        self.sums = None             # fp64 [3, T', nb]: S_p, S_t, S_x
-        self.frames = None           # int64 [T']: pairs added
+        super().reset()
         self.cells = None            # int64 [nb] (host): cells per bin
         self.hw = None               # (H, W) of the frames of this state
-        self._ws = None
 
     @property
     def wavenumber(self):
@@ -112,41 +100,32 @@ class SEVIRSpectralScore:
         with np.errstate(divide="ignore"):
             return 1.0 / self.wavenumber
 
-    def _alloc_state(self, dev, nb):
-        Tk = self.seq_len if self.keep_seq_len_dim else 1
-        self.sums = torch.zeros((3, Tk, nb), dtype=torch.float64, device=dev)
-        self.frames = torch.zeros((Tk,), dtype=torch.int64, device=dev)
+    def _alloc_state(self, dev):
+        """The number of bins comes from the frame sides: a rank that syncs before its first update sets `hw = (H, W)` first."""
+        if self.hw is None:
+            raise ValueError("sync() before any update: set .hw = (H, W) so that the zero state has the group's number of bins")
+        super()._alloc_state(dev)
+        if self.cells is None:
+            self.cells = spectrum_bins(*self.hw)[3]
 
     def update(self, pred: torch.Tensor, target: torch.Tensor):
-        if pred.dim() != len(self.layout) or tuple(pred.shape) != tuple(target.shape):
+        if pred.dim() != len(self.layout) or pred.shape != target.shape:
             raise ValueError(f"pred and target must have one shape in layout {self.layout!r}; got {tuple(pred.shape)} and "
                              f"{tuple(target.shape)}")
         self._launch(pred.unsqueeze(0), target)
 
     def update_members(self, ens: torch.Tensor, target: torch.Tensor):
-        if ens.dim() != len(self.layout) + 1 or tuple(ens.shape[1:]) != tuple(target.shape):
-            raise ValueError(f"ens must be (M,) + target.shape with target in layout {self.layout!r}; got {tuple(ens.shape)} "
-                             f"and {tuple(target.shape)}")
-        if not 1 <= ens.shape[0] <= MAX_MEMBERS:
-            raise ValueError(f"{ens.shape[0]} members: 1 .. {MAX_MEMBERS} are supported")
         self._launch(ens, target)
 
     def _launch(self, ens, target):
-        if not (ens.is_cuda and target.is_cuda):
-            raise L.PrediffHipError("SEVIRSpectralScore.update runs on the HIP device the frames were decoded on")
-        if self.keep_seq_len_dim:
-            assert target.shape[self.layout.find("T")] == self.seq_len
+        x, y, M, sizes, xs, ys = self._members(ens, target)
         dev = ens.device
-        x, y = ens.detach().float(), target.detach().float()          # read in place through their strides
-        M = x.shape[0]
-        sizes, xs = axes_of(self.layout, x, lead=1)
-        _, ys = axes_of(self.layout, y)
         H, W = int(sizes[2]), int(sizes[3])
         need = L.spectrum_ws_bytes(M, sizes)
         if need < 0:                             # an unsupported shape: the library refuses it before any launch and says which side
             i32, f64 = (torch.empty(1, dtype=d, device=dev) for d in (torch.int32, torch.float64))
             with L.on_device(ens):
-                L.spectrum_update(x, y, M, sizes, [x.stride(0)] + xs, ys, i32, i32, 0, 0, False, f64, i32, f64)
+                L.spectrum_update(x, y, M, sizes, xs, ys, i32, i32, 0, 0, False, f64, i32, f64)
             raise L.PrediffHipError(f"pd_spectrum_update: unsupported shape {tuple(sizes)}")
         if self.hw is not None and self.hw != (H, W):
             raise ValueError(f"frames of {H} x {W} after frames of {self.hw[0]} x {self.hw[1]}: reset() first, the bins differ")
@@ -155,43 +134,14 @@ class SEVIRSpectralScore:
             _, order, start, cells = spectrum_bins(H, W)
             self._bins[key] = (torch.from_numpy(order).to(dev), torch.from_numpy(start).to(dev), cells)
         order, start, cells = self._bins[key]
-        nb = cells.shape[0]
         self.hw, self.cells = (H, W), cells
-        if self.sums is None:
-            self._alloc_state(dev, nb)
-        elif self.sums.device != dev:            # a zero state that sync() made before this rank's first update
-            self.sums, self.frames = self.sums.to(dev), self.frames.to(dev)
+        self._state_on(dev)
         one = L.spectrum_ws_bytes(1, [1, 1, H, W, 1])
         want = max(one, min(need, int(WS_CAP_BYTES)))
-        if self._ws is None or self._ws.numel() * 8 < want or self._ws.device != dev:
-            self._ws = torch.empty((want + 7) // 8, dtype=torch.float64, device=dev)
-        ws = self._ws[:want // 8]                # an earlier, larger buffer does not lift the cap
+        ws = self._workspace((want + 7) // 8, torch.float64, dev)[:want // 8]       # an earlier, larger buffer does not lift the cap
         with L.on_device(ens):
-            L.spectrum_update(x, y, M, sizes, [x.stride(0)] + xs, ys, order, start, nb, WINDOWS.index(self.window),
+            L.spectrum_update(x, y, M, sizes, xs, ys, order, start, cells.shape[0], WINDOWS.index(self.window),
                               self.keep_seq_len_dim, self.sums, self.frames, ws)
-
-    def sync(self, group=None):
-        """All-reduce the state with SUM over the ranks of `group`; every rank must call it, including ranks that made no update
-        (they take part with a zero state; its number of bins comes from the frame sides, so such a rank sets `hw = (H, W)` first)."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        if self.sums is None:
-            if self.hw is None:
-                raise ValueError("sync() before any update: set .hw = (H, W) so that the zero state has the group's number of bins")
-            nccl = dist.get_backend(group) == "nccl"
-            self._alloc_state(torch.device("cuda", torch.cuda.current_device()) if nccl else torch.device("cpu"), max(self.hw) // 2 + 1)
-            self.cells = spectrum_bins(*self.hw)[3]
-        for t in (self.sums, self.frames):
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-
-    def _finish(self, per_t):
-        """per_t: (T', ...) -> the mode's form: [0] for "0", the array for "1", the mean over lead times for "2"."""
-        if self.mode == "0":
-            return per_t[0] if per_t.ndim > 1 else float(per_t[0])
-        if self.mode == "1":
-            return per_t
-        return np.mean(per_t, axis=0) if per_t.ndim > 1 else float(np.mean(per_t))
 
     def compute(self):
         Tk = self.seq_len if self.keep_seq_len_dim else 1
