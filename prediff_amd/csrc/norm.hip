@@ -289,10 +289,12 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__
   const int tid = threadIdx.x;
   double* out = partials + ((int64_t)b * nchunk + chunk) * G * 2;
   if ((C <= 256 && 256 % C == 0) || (C % 256 == 0)) {
-    // fast path: a thread always sees channels == tid (mod 256) -> one group per thread when cpg divides nicely
-    float s = 0.f, q = 0.f;
+    // fast path: a thread always sees channels == tid (mod 256) -> one group per thread when cpg divides nicely.  The sums are fp64 from
+    // the first add (x * x is exact there): gn_mean_rstd forms sumsq / n - mean^2, which multiplies the rounding of an fp32 sum of
+    // squares by (mean / std)^2
+    double s = 0, q = 0;
     if (C <= 256) {
-      for (int i = tid; i < n; i += 256) { const float v = xb[i]; s += v; q += v * v; }
+      for (int i = tid; i < n; i += 256) { const double v = xb[i]; s += v; q += v * v; }
       sred[tid * 2] = s; sred[tid * 2 + 1] = q;
       __syncthreads();
       if (tid < G) {
@@ -307,9 +309,9 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__
       for (int k = tid; k < G * 2; k += 256) sred[512 + k] = 0.0;
       __syncthreads();
       for (int cb = 0; cb < nblk; ++cb) {
-        float s2 = 0.f, q2 = 0.f;
+        double s2 = 0, q2 = 0;
         const int c = cb * 256 + tid;
-        for (int r = 0; r < r1 - r0; ++r) { const float v = xb[(int64_t)r * C + c]; s2 += v; q2 += v * v; }
+        for (int r = 0; r < r1 - r0; ++r) { const double v = xb[(int64_t)r * C + c]; s2 += v; q2 += v * v; }
         sred[tid * 2] = s2; sred[tid * 2 + 1] = q2;
         __syncthreads();
         // groups covered by this 256-column block: [cb*256/cpg, (cb*256+255)/cpg]
@@ -412,18 +414,20 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
 // ---- fast path: C % 4 == 0, (C/4) divides 256, channels-per-group % 4 == 0, ld_out == C.  A thread owns one float4
 // column (4 channels of ONE group) and walks rows; loads are 16 B/lane, stores 8 B/lane (bf16 x4). ----
 __global__ void __launch_bounds__(256) gn_stats_vec_kernel(const float* __restrict__ x, double* __restrict__ partials, int S, int C, int G) {
-  __shared__ float sred[256 * 2];
+  __shared__ double sred[256 * 2];
   const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
   const int CV = C >> 2, RP = 256 / CV;                 // float4 columns, rows per pass
   const int tid = threadIdx.x, cv = tid % CV, rr = tid / CV;
   const int r0 = chunk * GN_ROWS, r1 = min(S, r0 + GN_ROWS);
   const float4* xb = (const float4*)(x + ((int64_t)b * S + r0) * C) + cv;
-  float s = 0.f, q = 0.f;
+  // fp64 from the first add, like gn_stats_kernel (the kernel streams HBM: a convert and two fp64 operations per element are hidden)
+  double s = 0, q = 0;
 #pragma unroll 4
   for (int r = rr; r < r1 - r0; r += RP) {
     const float4 v = xb[(int64_t)r * CV];
-    s += (v.x + v.y) + (v.z + v.w);
-    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    const double v0 = v.x, v1 = v.y, v2 = v.z, v3 = v.w;
+    s += (v0 + v1) + (v2 + v3);
+    q += (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
   }
   sred[tid * 2] = s;
   sred[tid * 2 + 1] = q;
@@ -885,7 +889,9 @@ __global__ void __launch_bounds__(256) gn_silu_bwd_kernel(const float* __restric
   const int c = tid % C, rr = tid / C, RP = 256 / C, g = c / cpg;
   const float2 mr = gn_mean_rstd(sfwd[g * 2], sfwd[g * 2 + 1], cnt, eps);
   const float mean = mr.x, rstd = mr.y;
-  const float ga = gamma[c], a = rstd * ga, d = beta[c] - mean * a;
+  // n from the centred xh, not from the folded x * (rstd gamma) + (beta - mean rstd gamma): the fold rounds at |mean| rstd, which on a
+  // near-constant group (rstd up to 1 / sqrt(eps)) is 1e-4 of n, the same way in every row -- it adds up in the partial sums
+  const float ga = gamma[c], be = beta[c];
   const float m1 = APPLY ? (float)(sbwd[g * 2] / cnt) : 0.f, m2 = APPLY ? (float)(sbwd[g * 2 + 1] / cnt) : 0.f;
   const int r0 = chunk * GN_ROWS, r1 = min(S, r0 + GN_ROWS);
   const int64_t base = ((int64_t)b * S + r0) * C + c;
@@ -893,13 +899,13 @@ __global__ void __launch_bounds__(256) gn_silu_bwd_kernel(const float* __restric
 #pragma unroll 4
   for (int r = rr; r < r1 - r0; r += RP) {
     const float xv = x[base + (int64_t)r * C], gy = dy[base + (int64_t)r * C];
-    const float n = xv * a + d;
+    const float xh = (xv - mean) * rstd, n = xh * ga + be;
     float dn = gy;
     if (silu) {
       const float sig = 1.f / (1.f + __expf(-n));
       dn = gy * sig * (1.f + n * (1.f - sig));
     }
-    const float dxh = dn * ga, xh = (xv - mean) * rstd;
+    const float dxh = dn * ga;
     if (APPLY) {
       dx[base + (int64_t)r * C] = rstd * (dxh - m1 - xh * m2);
     } else {

@@ -17,6 +17,7 @@ Same constructor keywords and call conventions; what changes:
 The knowledge-alignment hook (`set_alignment`) is honoured with the reference semantics; its gradient stays in
 PyTorch autograd (north_star) and therefore runs outside the captured graph.
 """
+import gc
 from typing import Any, Callable, Dict, Optional, Sequence, Union
 
 import numpy as np
@@ -438,9 +439,20 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                 body()
         torch.cuda.current_stream(device).wait_stream(side)
         torch.cuda.synchronize(device)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            body()
+        # No cyclic collection inside the capture.  A dead cycle from earlier work may own HIP resources (an older LatentDiffusion's
+        # CUDAGraph, whose destructor synchronises the device on ROCm; device tensors), and finalising those is a call the capture
+        # forbids: it throws inside a destructor and the process aborts.  torch.cuda.graph used to collect on entry; since torch 2.9 it
+        # does so only under torch.compiler.config.force_cudagraph_gc.  So collect here, once per capture, and hold the collector off.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                body()
+        finally:
+            if gc_was_on:
+                gc.enable()
         if hasattr(net, "_ws_slot"):
             net._ws_slot = 0
         st["graph"] = graph

@@ -353,7 +353,7 @@ def test_layernorm(rows, Cn):
     assert float(out[:, Cn:].float().abs().max() if ld > Cn else 0) == 0
 
 
-@pytest.mark.parametrize("T,H,W,Cn", [(3, 8, 8, 64), (13, 16, 16, 256), (3, 7, 6, 16)])
+@pytest.mark.parametrize("T,H,W,Cn", [(3, 8, 8, 64), (13, 16, 16, 256), (3, 7, 6, 16), (3, 7, 5, 16)])
 def test_patch_merge_layernorm(T, H, W, Cn):
     B = 2
     g = torch.Generator(device="cpu").manual_seed(T * H)
@@ -368,6 +368,25 @@ def test_patch_merge_layernorm(T, H, W, Cn):
     xm = xp.reshape(B, T, 1, Ho, 2, Wo, 2, Cn).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(B * T * Ho * Wo, 4 * Cn)
     ref = F.layer_norm(xm, (4 * Cn,), gamma, beta, 1e-5)
     assert rel_l2(out[:, :4 * Cn].float() + lo[:, :4 * Cn].float(), ref) < 2e-5
+
+
+# padding_type "nearest" and zeros, H and W both odd, more than one padded position per axis (9 -> 12: the float32 scale of torch's
+# nearest rule), T padded as well: every element of hi + lo against the fp64 gather + LayerNorm of tests/_norm_ref.py
+@pytest.mark.parametrize("nearest", [True, False])
+@pytest.mark.parametrize("T,H,W,Cn,ds", [(3, 7, 5, 16, (1, 2, 2)), (2, 9, 7, 8, (1, 4, 4)), (3, 5, 6, 4, (2, 2, 2))])
+def test_patch_merge_layernorm_padding(T, H, W, Cn, ds, nearest):
+    import _norm_ref as R
+    B = 2
+    g = torch.Generator(device="cpu").manual_seed(T * H + W)
+    x = torch.randn(B, T, H, W, Cn, generator=g).to(DEV)
+    Cm = Cn * ds[0] * ds[1] * ds[2]
+    gamma, beta = (1 + 0.1 * torch.randn(Cm, generator=g)).to(DEV), torch.randn(Cm, generator=g).to(DEV)
+    rows, ld = B * math.prod(-(-n // d) for n, d in zip((T, H, W), ds)), L.pad64(Cm)
+    out = torch.full((rows, ld), 7.0, dtype=torch.bfloat16, device=DEV)
+    lo = torch.full_like(out, 7.0)
+    L.patch_merge_layernorm(x, gamma, beta, out, lo, B, T, H, W, Cn, ds, ld, pad_nearest=nearest)
+    spec = dict(op="patch_merge_layernorm", x=x, gamma=gamma, beta=beta, eps=1e-5, ld=ld, fmt="hilo", ds=ds, nearest=nearest)
+    R.verify(f"patch_merge_layernorm {T}x{H}x{W}x{Cn} ds {ds} nearest {nearest}", spec, {"out": out, "lo": lo})
 
 
 @pytest.mark.parametrize("B,S,Cn,G", [(2, 3328, 256, 32), (2, 832, 512, 32), (2, 320, 5, 5), (3, 100, 65, 65), (2, 64, 64, 32),
