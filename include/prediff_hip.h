@@ -366,6 +366,31 @@ int pd_dpmpp_2m_sde_step(const float* zt, const float* eps, const float* noise, 
 int pd_dpmpp_2m_sde_step_guided(const float* zt, const float* eps, const float* noise, float* hist, const float* shift, const float* coef6,
                                 float* out, int B, int64_t per_sample, pd_stream_t stream);
 
+/* Held-region (inpainting) forms of the three step kernels ("Held regions"): the step and the hold in one launch.
+ *   v    = the un-held kernel's result, the same operations in the same order (shift == NULL: un-guided, gamma is not read)
+ *   held = k_n != 0 ? k_x hold_x0 + k_n hold_noise : k_x hold_x0
+ *   out  = m == 0 ? v : m == 1 ? held : m held + (1 - m) v          with m = hold_mask, fp32 in [0, 1], 1 = held
+ *   The two end points are selects: where m == 0 the output is the un-held kernel's bit for bit whatever hold_x0 / hold_noise hold
+ *   (NaN included), where m == 1 nothing of v reaches it, and with the row (k_x, k_n) = (1, 0) it is hold_x0 bit for bit there.
+ *   hold_x0 / hold_mask / hold_noise: fp32 like zt.  k_n is per sample: hold_noise is not read where k_n == 0 (it may hold anything),
+ *   but the pointer must not be NULL.  hist is read and written as in the un-held kernels.  out must not alias an input.
+ *   Coefficient rows, fp32 per sample (the un-held row, gamma, then k_x = sqrt(u), k_n = sqrt(1 - u); schedule.make_hold_coefficients):
+ *     pd_ddim_step_held          coef6 (B,6): [a_t, a_prev, sigma, gamma, k_x, k_n]      noise may be NULL (eta = 0), as pd_ddim_step
+ *     pd_dpmpp_2m_step_held      coef7 (B,7): [a_t, c_x, c_d, w, gamma, k_x, k_n]
+ *     pd_dpmpp_2m_sde_step_held  coef8 (B,8): [a_t, c_x, c_d, w, c_n, gamma, k_x, k_n]   noise is not read where c_n == 0 */
+int pd_ddim_step_held(const float* zt, const float* eps, const float* noise, const float* shift, const float* hold_x0, const float* hold_mask,
+                      const float* hold_noise, const float* coef6, float* out, int B, int64_t per_sample, pd_stream_t stream);
+int pd_dpmpp_2m_step_held(const float* zt, const float* eps, float* hist, const float* shift, const float* hold_x0, const float* hold_mask,
+                          const float* hold_noise, const float* coef7, float* out, int B, int64_t per_sample, pd_stream_t stream);
+int pd_dpmpp_2m_sde_step_held(const float* zt, const float* eps, const float* noise, float* hist, const float* shift, const float* hold_x0,
+                              const float* hold_mask, const float* hold_noise, const float* coef8, float* out, int B, int64_t per_sample,
+                              pd_stream_t stream);
+
+/* The start rule of a held run: out = <the select above> with v = z and the rows coef2 (B,2) = [k_x, k_n] = [sqrt(a_0), sqrt(1 - a_0)].
+ *   out may alias z, and noise may be z itself (the starting latent is the noise of the held part). */
+int pd_hold_blend(const float* z, const float* x0, const float* mask, const float* noise, const float* coef2, float* out, int B,
+                  int64_t per_sample, pd_stream_t stream);
+
 /* Tiled sampling on a canvas larger than the model's window (prediff_amd/tiled.py).  Channels-last fp32 throughout.
  *   canvas (B, T, Hc, Wc, C); windows (B, nwin, T, h, w, C), batch-major; origin_yx (nwin, 2) int32 ON THE DEVICE, the (y, x) of each
  *   window's first cell, 0 <= y <= Hc - h and 0 <= x <= Wc - w (the library cannot read the table: the caller checks it.  A window

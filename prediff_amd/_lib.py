@@ -154,6 +154,10 @@ _PROTOS = {
     "pd_dpmpp_2m_step_guided": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_dpmpp_2m_sde_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_dpmpp_2m_sde_step_guided": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_ddim_step_held": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_dpmpp_2m_step_held": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_dpmpp_2m_sde_step_held": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int64, C.c_void_p]),
+    "pd_hold_blend": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_void_p]),
     "pd_window_gather": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
     "pd_window_blend": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),
     "pd_context_advance": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.c_float] + [C.c_int] * 3 + [C.c_void_p]),
@@ -614,6 +618,47 @@ def dpmpp_2m_sde_step_guided(zt, eps, noise, hist, shift, coef6, out, B, per_sam
                                                       ("shift", shift, n), ("coef6", coef6, 6 * B), ("out", out, n)))
     _check(lib().pd_dpmpp_2m_sde_step_guided(ptr(zt), ptr(eps), ptr(noise), ptr(hist), ptr(shift), ptr(coef6), ptr(out), B, per_sample,
                                              stream_ptr()), "pd_dpmpp_2m_sde_step_guided")
+
+
+def _held_operands(fn, B, per_sample, width, coef, named):
+    """Operand check of the held step kernels: every given tensor covers B * per_sample elements, the rows B * width; `shift` and DDIM's
+    `noise` may be None."""
+    n = B * per_sample
+    _check_step_operands(fn, tuple((name, x, n) for name, x in named if x is not None) + ((f"coef{width}", coef, width * B),))
+    for name, x in named:
+        if x is None and name not in ("shift", "noise"):
+            raise PrediffHipError(f"{fn}: {name} must not be None")
+
+
+def ddim_step_held(zt, eps, noise, shift, hold_x0, hold_mask, hold_noise, coef6, out, B, per_sample):
+    """pd_ddim_step[_guided] and the hold in one launch (coef6 rows: a_t, a_prev, sigma, gamma, k_x, k_n); `noise` may be None (eta = 0),
+    `shift` None is the un-guided step; `hold_noise` is read only where k_n != 0."""
+    _held_operands("ddim_step_held", B, per_sample, 6, coef6, (("zt", zt), ("eps", eps), ("noise", noise), ("shift", shift),
+                   ("hold_x0", hold_x0), ("hold_mask", hold_mask), ("hold_noise", hold_noise), ("out", out)))
+    _check(lib().pd_ddim_step_held(ptr(zt), ptr(eps), ptr(noise), ptr(shift), ptr(hold_x0), ptr(hold_mask), ptr(hold_noise), ptr(coef6),
+                                   ptr(out), B, per_sample, stream_ptr()), "pd_ddim_step_held")
+
+
+def dpmpp_2m_step_held(zt, eps, hist, shift, hold_x0, hold_mask, hold_noise, coef7, out, B, per_sample):
+    """pd_dpmpp_2m_step[_guided] and the hold in one launch (coef7 rows: a_t, c_x, c_d, w, gamma, k_x, k_n)."""
+    _held_operands("dpmpp_2m_step_held", B, per_sample, 7, coef7, (("zt", zt), ("eps", eps), ("hist", hist), ("shift", shift),
+                   ("hold_x0", hold_x0), ("hold_mask", hold_mask), ("hold_noise", hold_noise), ("out", out)))
+    _check(lib().pd_dpmpp_2m_step_held(ptr(zt), ptr(eps), ptr(hist), ptr(shift), ptr(hold_x0), ptr(hold_mask), ptr(hold_noise), ptr(coef7),
+                                       ptr(out), B, per_sample, stream_ptr()), "pd_dpmpp_2m_step_held")
+
+
+def dpmpp_2m_sde_step_held(zt, eps, noise, hist, shift, hold_x0, hold_mask, hold_noise, coef8, out, B, per_sample):
+    """pd_dpmpp_2m_sde_step[_guided] and the hold in one launch (coef8 rows: a_t, c_x, c_d, w, c_n, gamma, k_x, k_n)."""
+    _held_operands("dpmpp_2m_sde_step_held", B, per_sample, 8, coef8, (("zt", zt), ("eps", eps), ("sde noise", noise), ("hist", hist),
+                   ("shift", shift), ("hold_x0", hold_x0), ("hold_mask", hold_mask), ("hold_noise", hold_noise), ("out", out)))
+    _check(lib().pd_dpmpp_2m_sde_step_held(ptr(zt), ptr(eps), ptr(noise), ptr(hist), ptr(shift), ptr(hold_x0), ptr(hold_mask),
+                                           ptr(hold_noise), ptr(coef8), ptr(out), B, per_sample, stream_ptr()), "pd_dpmpp_2m_sde_step_held")
+
+
+def hold_blend(z, x0, mask, noise, coef2, out, B, per_sample):
+    """The start rule of a held run: out = mask-select of z and k_x x0 + k_n noise (coef2 rows: k_x, k_n); `out` may be `z`."""
+    _held_operands("hold_blend", B, per_sample, 2, coef2, (("z", z), ("x0", x0), ("mask", mask), ("hold noise", noise), ("out", out)))
+    _check(lib().pd_hold_blend(ptr(z), ptr(x0), ptr(mask), ptr(noise), ptr(coef2), ptr(out), B, per_sample, stream_ptr()), "pd_hold_blend")
 
 
 _origin_tables = {}      # (table bytes, canvas, window, device, covering) -> the checked device copy

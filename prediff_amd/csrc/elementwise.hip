@@ -458,6 +458,126 @@ extern "C" int pd_dpmpp_2m_sde_step_guided(const float* zt, const float* eps, co
   return PD_OK;
 }
 
+// ---- held-region (inpainting) forms of the three step kernels ("Held regions") ----
+// The step's own result v, then  held = k_x x0 + k_n hnoise  and  out = m == 0 ? v : m == 1 ? held : m held + (1 - m) v  in the same
+// launch.  Rows: the un-held row, gamma (read only with a shift pointer), then (k_x, k_n).  v is spelled with the operations the
+// un-held kernels compile to (the products they fuse are explicit FMAs here, and contraction is off, so nothing else is fused): where
+// m == 0 the output is theirs bit for bit.  The two end points of the mask are selects: a NaN in x0 / hnoise under m == 0, or in v under
+// m == 1, stays where it is.  k_n is per sample like w and c_n: with k_n == 0 (the last step) hnoise is NOT read.
+__device__ __forceinline__ float hold_select(float v, float m, float x0, const float* hnoise, int64_t j, float k_x, float k_n) {
+#pragma clang fp contract(off)
+  float held = k_x * x0;
+  if (k_n != 0.f) held = fmaf(k_n, hnoise[j], held);
+  const float mix = fmaf(m, held, (1.f - m) * v);
+  return m == 0.f ? v : m == 1.f ? held : mix;
+}
+
+__global__ void __launch_bounds__(256) ddim_step_held_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
+                                                             const float* __restrict__ noise, const float* __restrict__ shift,
+                                                             const float* __restrict__ x0, const float* __restrict__ mask,
+                                                             const float* __restrict__ hnoise, const float* __restrict__ coef,
+                                                             float* __restrict__ out, int64_t per) {
+#pragma clang fp contract(off)
+  constexpr int NC = 6;                          // a_t, a_prev, sigma, gamma, k_x, k_n
+  const int b = blockIdx.y;
+  const float a_t = coef[b * NC], a_prev = coef[b * NC + 1], sigma = coef[b * NC + 2], gamma = coef[b * NC + 3];
+  const float k_x = coef[b * NC + 4], k_n = coef[b * NC + 5];
+  const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t), sp = sqrtf(a_prev);
+  const float dir = sqrtf(fmaxf(0.f, fmaf(-sigma, sigma, 1.f - a_prev)));
+  const int64_t base = (int64_t)b * per;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
+    const float e = eps[base + i];
+    const float z0 = fmaf(-s1, e, zt[base + i]) * r;
+    float v = fmaf(dir, e, sp * z0) + (noise ? sigma * noise[base + i] : 0.f);
+    if (shift) v = fmaf(-gamma, shift[base + i], v);
+    out[base + i] = hold_select(v, mask[base + i], x0[base + i], hnoise, base + i, k_x, k_n);
+  }
+}
+
+// SDE = false: rows (a_t, c_x, c_d, w, gamma, k_x, k_n) and no noise pointer; SDE = true: rows (a_t, c_x, c_d, w, c_n, gamma, k_x, k_n)
+template <bool SDE>
+__global__ void __launch_bounds__(256) dpmpp_2m_step_held_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
+                                                                 const float* __restrict__ noise, float* __restrict__ hist,
+                                                                 const float* __restrict__ shift, const float* __restrict__ x0,
+                                                                 const float* __restrict__ mask, const float* __restrict__ hnoise,
+                                                                 const float* __restrict__ coef, float* __restrict__ out, int64_t per) {
+#pragma clang fp contract(off)
+  constexpr int NC = SDE ? 8 : 7, G = SDE ? 5 : 4;
+  const int b = blockIdx.y;
+  const float a_t = coef[b * NC], c_x = coef[b * NC + 1], c_d = coef[b * NC + 2], w = coef[b * NC + 3];
+  const float c_n = SDE ? coef[b * NC + 4] : 0.f;
+  const float gamma = coef[b * NC + G], k_x = coef[b * NC + G + 1], k_n = coef[b * NC + G + 2];
+  const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t);
+  const bool second_order = w != 0.f, stochastic = c_n != 0.f;
+  const int64_t base = (int64_t)b * per;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
+    const float z = zt[base + i];
+    const float z0 = fmaf(-s1, eps[base + i], z) * r;
+    float d = z0;
+    if (second_order) d = fmaf(w, z0 - hist[base + i], z0);
+    float v = fmaf(c_d, d, c_x * z);
+    if constexpr (SDE) {
+      if (stochastic) v = fmaf(c_n, noise[base + i], v);
+    }
+    if (shift) v = fmaf(-gamma, shift[base + i], v);
+    out[base + i] = hold_select(v, mask[base + i], x0[base + i], hnoise, base + i, k_x, k_n);
+    hist[base + i] = z0;
+  }
+}
+
+#define PD_CHECK_HOLD(fn) \
+  PD_CHECK_ARG(hold_x0 && hold_mask && hold_noise, fn ": hold_x0 / hold_mask / hold_noise must not be null (hold_noise is not read where k_n == 0)")
+
+extern "C" int pd_ddim_step_held(const float* zt, const float* eps, const float* noise, const float* shift, const float* hold_x0,
+                                 const float* hold_mask, const float* hold_noise, const float* coef6, float* out, int B, int64_t per_sample,
+                                 pd_stream_t stream) {
+  PD_CHECK_ARG(zt && eps && coef6 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_ddim_step_held: bad args");
+  PD_CHECK_HOLD("pd_ddim_step_held");
+  hipLaunchKernelGGL(ddim_step_held_kernel, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, shift, hold_x0,
+                     hold_mask, hold_noise, coef6, out, per_sample);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+extern "C" int pd_dpmpp_2m_step_held(const float* zt, const float* eps, float* hist, const float* shift, const float* hold_x0,
+                                     const float* hold_mask, const float* hold_noise, const float* coef7, float* out, int B,
+                                     int64_t per_sample, pd_stream_t stream) {
+  PD_CHECK_ARG(zt && eps && hist && coef7 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_step_held: bad args");
+  PD_CHECK_HOLD("pd_dpmpp_2m_step_held");
+  hipLaunchKernelGGL(dpmpp_2m_step_held_kernel<false>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps,
+                     (const float*)nullptr, hist, shift, hold_x0, hold_mask, hold_noise, coef7, out, per_sample);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+extern "C" int pd_dpmpp_2m_sde_step_held(const float* zt, const float* eps, const float* noise, float* hist, const float* shift,
+                                         const float* hold_x0, const float* hold_mask, const float* hold_noise, const float* coef8, float* out,
+                                         int B, int64_t per_sample, pd_stream_t stream) {
+  PD_CHECK_ARG(zt && eps && noise && hist && coef8 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_sde_step_held: bad args");
+  PD_CHECK_HOLD("pd_dpmpp_2m_sde_step_held");
+  hipLaunchKernelGGL(dpmpp_2m_step_held_kernel<true>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, hist,
+                     shift, hold_x0, hold_mask, hold_noise, coef8, out, per_sample);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
+// the start rule: out = hold_select(z, ...) with rows (k_x, k_n) = (sqrt(a_0), sqrt(1 - a_0)).  Every element is read, then written, by
+// the one thread that owns it (no __restrict__ on z / noise / out): out may alias z, and noise may be z itself.
+__global__ void __launch_bounds__(256) hold_blend_kernel(const float* z, const float* __restrict__ x0, const float* __restrict__ mask,
+                                                         const float* noise, const float* __restrict__ coef, float* out, int64_t per) {
+  const int b = blockIdx.y;
+  const float k_x = coef[b * 2], k_n = coef[b * 2 + 1];
+  const int64_t base = (int64_t)b * per;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256)
+    out[base + i] = hold_select(z[base + i], mask[base + i], x0[base + i], noise, base + i, k_x, k_n);
+}
+extern "C" int pd_hold_blend(const float* z, const float* x0, const float* mask, const float* noise, const float* coef2, float* out, int B,
+                             int64_t per_sample, pd_stream_t stream) {
+  PD_CHECK_ARG(z && x0 && mask && noise && coef2 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_hold_blend: bad args");
+  hipLaunchKernelGGL(hold_blend_kernel, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, z, x0, mask, noise, coef2, out,
+                     per_sample);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
+
 // ---- NCHW <-> NHWC (fp32) ----
 __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ out, int N, int C, int HW, int ld) {
   const int64_t total = (int64_t)N * HW * ld;

@@ -72,12 +72,14 @@ def sample_ensemble(ldm, cond, num_members: int, base_seed: int = 0, sampler: st
                     timesteps: Optional[int] = None, micro_batch: Optional[int] = None, group=None, return_decoded: bool = True,
                     use_alignment: bool = False, alignment_kwargs=None, sample_fn: Optional[Callable] = None,
                     force_collective: bool = False, steps: Optional[int] = None, discretize: str = "quad",
-                    lower_order_final: Optional[bool] = None) -> torch.Tensor:
+                    lower_order_final: Optional[bool] = None, hold_mask=None, hold_x0=None, hold_noise: str = "fresh") -> torch.Tensor:
     """Draw `num_members` samples for ONE context (cond["y"]: (1, T_in, H, W, C)) across all ranks of `group`.
     sampler="dpmpp_2m" takes `steps` (default 20), `discretize` and `lower_order_final` (LatentDiffusion.dpmpp_2m_sample_loop); it reads
     draw 0 of each member's noise only.  sampler="dpmpp_2m_sde" takes the same keywords and `eta` (dpmpp_2m_sde_sample_loop); this
     function's `eta` defaults to 0.0, which reaches that sampler as the deterministic solver: pass eta=1.0 for the stochastic one.  Its
     step k reads draw 1 + k of each member's own generator, so a member does not depend on the batch split or the world size.
+    hold_mask / hold_x0 / hold_noise: ``sample``'s held region ("Held regions"); a batch of 1 holds every member to the
+    same latent, a batch of `num_members` is cut per member.  The hold draws come from the members' own generators, in step order.
 
     Returns (num_members, T_out, H, W, C) on every rank.  `sample_fn(cond_batch, batch, noise_fn)` can replace the call into
     `ldm.sample` (used by the CPU gloo tests of the sharding logic)."""
@@ -105,6 +107,11 @@ def sample_ensemble(ldm, cond, num_members: int, base_seed: int = 0, sampler: st
             ak = {k: (v.expand(len(ks), *v.shape[1:]) if torch.is_tensor(v) and v.shape[0] == 1 else v) for k, v in alignment_kwargs.items()}
         kw = dict(batch_size=len(ks), return_decoded=return_decoded, noise_tape=_LazyTape(noise), use_alignment=use_alignment,
                   alignment_kwargs=ak)
+        if hold_mask is not None or hold_x0 is not None:
+            def mine_of(v):      # a per-member hold is cut to this micro-batch; a batch of 1 (or a broadcastable mask) goes as it is
+                per_member = torch.is_tensor(v) and v.dim() == len(latent_shape) + 1 and v.shape[0] == num_members and num_members > 1
+                return v[torch.as_tensor(ks, device=v.device)] if per_member else v
+            kw.update(hold_mask=mine_of(hold_mask), hold_x0=mine_of(hold_x0), hold_noise=hold_noise)
         if sampler == "ddim":
             out = ldm.sample(cb, sampler="ddim", ddim_steps=ddim_steps, eta=eta, **kw)
         elif sampler == "dpmpp_2m":

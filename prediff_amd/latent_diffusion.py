@@ -11,7 +11,9 @@ Same constructor keywords and call conventions; what changes:
     only refreshes t / noise, so small batches are not launch-bound;
   * a DDIM sampler exists (the reference ships only the two schedule helpers): ``sample(...,
     sampler="ddim", ddim_steps=50, eta=0.)``, and a second-order multistep one, DPM-Solver++(2M): ``sample(..., sampler="dpmpp_2m",
-    steps=20, discretize="quad")``, with a stochastic form, ``sampler="dpmpp_2m_sde", eta=1.0``;
+    steps=20, discretize="quad")``, with a stochastic form, ``sampler="dpmpp_2m_sde", eta=1.0``; these three hold a region of the
+    latent with ``hold_mask`` / ``hold_x0`` ("Held regions"), fused into the same step-epilogue launch, while the
+    reference's ``mask`` / ``x0`` keep their meaning on the ancestral loop;
   * of the training side, everything that needs no gradient is here (q_sample, forward / p_losses as loss VALUES, LitEma + ema_scope,
     validation_step); training_step raises: there is no backward pass through the HIP kernels.
 The knowledge-alignment hook (`set_alignment`) is honoured with the reference semantics; its gradient stays in
@@ -29,7 +31,12 @@ from .distributions import DiagonalGaussianDistribution
 from .ema import LitEma
 from .loss_eval import LossEvaluationMixin
 from .schedule import (make_beta_schedule, make_ddim_guidance_coefficients, make_ddim_sampling_parameters, make_ddim_timesteps,
-                       make_dpmpp_2m_coefficients, make_dpmpp_2m_sde_coefficients, make_logsnr_timesteps, schedule_tables)
+                       make_dpmpp_2m_coefficients, make_dpmpp_2m_sde_coefficients, make_hold_coefficients, make_logsnr_timesteps,
+                       schedule_tables)
+
+HOLD_NOISE = ("fresh", "fixed")
+# fp32 columns of a step's coefficient row per graph kind; the "_held" kinds carry (gamma, k_x, k_n) behind the un-held row
+_COEF_WIDTH = {"dpmpp": 4, "dpmpp_sde": 5, "ddim_held": 6, "dpmpp_held": 7, "dpmpp_sde_held": 8}
 
 
 def parse_layout_shape(layout: str) -> Dict[str, int]:
@@ -413,18 +420,29 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         shape = self.get_batch_latent_shape(B)
         st = dict(z=torch.zeros(shape, device=device), noise=torch.zeros(shape, device=device),
                   t=torch.zeros(B, dtype=torch.int64, device=device), out=torch.zeros(shape, device=device),
-                  coef=torch.zeros(B, {"dpmpp": 4, "dpmpp_sde": 5}.get(kind, 3), device=device), zc=zc.detach().clone().float().contiguous())
-        if kind in ("dpmpp", "dpmpp_sde"):   # the previous step's x0; every loop's first step has w = 0 and does not read it
+                  coef=torch.zeros(B, _COEF_WIDTH.get(kind, 3), device=device), zc=zc.detach().clone().float().contiguous())
+        if kind.startswith("dpmpp"):         # the previous step's x0; every loop's first step has w = 0 and does not read it
             st["hist"] = torch.zeros(shape, device=device)
+        held = kind.endswith("_held")        # held-region run: the known latent, the mask and the hold's noise are static inputs too
+        if held:
+            st.update({k: torch.zeros(shape, device=device) for k in ("hold_x0", "hold_mask", "hold_noise")})
 
         def body():
             if hasattr(net, "_ws_slot"):
                 net._ws_slot = lane
             eps = self.apply_model(st["z"], st["t"], st["zc"])
+            if held:
+                hold = (st["hold_x0"], st["hold_mask"], st["hold_noise"], st["coef"], st["out"], B, st["z"][0].numel())
             if kind == "eps":            # denoiser only: the step epilogue needs the alignment shift, computed outside the graph
                 st["out"].copy_(eps)
             elif kind == "ddpm":
                 self._ddpm_update(st["z"], eps, st["noise"], None, st["t"], 1.0, self.clip_denoised, out=st["out"])
+            elif kind == "ddim_held":
+                L.ddim_step_held(st["z"], eps, st["noise"], None, *hold)
+            elif kind == "dpmpp_held":
+                L.dpmpp_2m_step_held(st["z"], eps, st["hist"], None, *hold)
+            elif kind == "dpmpp_sde_held":
+                L.dpmpp_2m_sde_step_held(st["z"], eps, st["noise"], st["hist"], None, *hold)
             elif kind == "dpmpp":
                 L.dpmpp_2m_step(st["z"], eps, st["hist"], st["coef"], st["out"], B, st["z"][0].numel())
             elif kind == "dpmpp_sde":
@@ -580,7 +598,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
 
     def _run_sampler(self, kind, cond, shape, x_T, noise_tape, visits, epilogue, coefs=None, draw=None, eager=None,
                      use_alignment=False, y=None, alignment_kwargs=None, return_intermediates=False, log_every_t=1, mask=None,
-                     x0=None, callback=None, img_callback=None):
+                     x0=None, callback=None, img_callback=None, hold=None):
         """The step loop of every sampler.  One of four modes is chosen once per call:
           lanes   -- one `kind` graph per equal sub-batch, each replayed on its own stream (no per-step hooks; see _lanes);
           graph   -- one `kind` graph replayed on the caller's stream;
@@ -591,10 +609,21 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         visits: (t, row) per step in visiting order; `row` picks the step's coefficients from the device table `coefs`.
         epilogue(cur, eps, shift, ts, row, noise) -> the next latent; `shift` is None without alignment.
         Step noise: _step_noise, drawn from the device generator at the start of the step with draw="early", where the step
-        needs it with draw="late" (the reference's ancestral order: after the denoiser and the guidance), zero with None."""
+        needs it with draw="late" (the reference's ancestral order: after the denoiser and the guidance), zero with None.
+        hold: a held-region run (_hold_operands; DESIGN.md §7, "Held regions") in any of the four modes: the graphs are the "_held" kinds,
+        whose step kernel blends the known latent in, and `epilogue` gets the hold's noise as a seventh argument.  The start rule is one
+        pd_hold_blend launch.  The hold draw of step k follows the step's own tape entry (hold["tape_own"]) or stands in its place."""
         device = self.betas.device
         B = shape[self.batch_axis]
         img = self._start_latent(x_T, noise_tape, shape, device)
+        fresh = own = False
+        if hold is not None:
+            fresh, own = hold["fresh"], hold["tape_own"]
+            x_T = img.contiguous().float()             # the noise of the held part at the start, and at every step with "fixed"
+            img = torch.empty_like(x_T)
+            with L.on_device(x_T):
+                L.hold_blend(x_T, hold["x0"], hold["mask"], x_T, hold["start"].expand(B, 2).contiguous(), img, B, x_T[0].numel())
+            kind = kind + "_held"
 
         def randn():
             return torch.randn(shape, device=device)
@@ -612,12 +641,26 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             sts, _, Bl = lanes
             for l, st in enumerate(sts):
                 st["z"].copy_(img[l * Bl:(l + 1) * Bl])
+        if hold is not None and graph is not None:     # the static hold inputs of every lane, refreshed per call
+            sts, _, Bl = graph
+            for l, st in enumerate(sts):
+                sl = slice(l * Bl, (l + 1) * Bl)
+                st["hold_x0"].copy_(hold["x0"][sl])
+                st["hold_mask"].copy_(hold["mask"][sl])
+                if not fresh:
+                    st["hold_noise"].copy_(x_T[sl])
         intermediates = [img]
+        # tape entries per step: [c_k, n_k] with shorten_cond_schedule; [n_k][, h_k] of a held run (n_k only where the step reads one)
+        per_step = 1 + shorten if hold is None else int(own) + int(fresh)
         for k, (t, row) in enumerate(visits):
             if shorten:      # the conditioning latents re-noised in front of the step (cumulative, as in the reference)
                 cn = self._step_noise(noise_tape, k, device, lambda: torch.randn_like(cond), per_step=2)
                 cond = self.q_sample(cond, self.cond_ids[torch.full((B,), t, device=device, dtype=torch.long)], noise=cn)
-            noise = self._step_noise(noise_tape, k, device, randn if draw == "early" else None, 1 + shorten, int(shorten))
+            noise = self._step_noise(noise_tape if hold is None or own else None, k, device, randn if draw == "early" else None, per_step,
+                                     int(shorten))
+            hn = None                                  # the last step has k_n = 0: it draws nothing and its kernel reads nothing
+            if hold is not None and k < len(visits) - 1:
+                hn = self._step_noise(noise_tape, k, device, randn, per_step, int(own)) if fresh else x_T
             if graph is not None:
                 if noise is None and draw == "late" and lanes is not None:
                     noise = randn()               # one whole-batch draw (the reference's RNG order), sliced per lane
@@ -632,7 +675,9 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                         st["noise"].copy_(noise[sl])
                     else:
                         st["noise"].normal_() if draw == "late" else st["noise"].zero_()
-                self._lane_step(*graph, device, fill, keep=(noise,), advance=lanes is not None)
+                    if fresh and hn is not None:
+                        st["hold_noise"].copy_(hn[sl])
+                self._lane_step(*graph, device, fill, keep=(noise, hn), advance=lanes is not None)
                 if lanes is None:
                     img = graph[0][0]["out"].clone()
             else:
@@ -648,7 +693,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                         shift = self._guidance(cur, ts, cond, y, alignment_kwargs) if use_alignment else None
                     if noise is None and draw == "late":
                         noise = randn()
-                    img = epilogue(cur, eps, shift, ts, row, noise)
+                    img = epilogue(cur, eps, shift, ts, row, noise) if hold is None else epilogue(cur, eps, shift, ts, row, noise, hn)
             if mask is not None:
                 img = self.q_sample(x0, torch.full((B,), t, device=device, dtype=torch.long)) * mask + (1.0 - mask) * img
             if return_intermediates and (t % log_every_t == 0 or k == 0):
@@ -688,16 +733,83 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                                  return_intermediates=return_intermediates, log_every_t=log_every_t or self.log_every_t, mask=mask,
                                  x0=x0, callback=callback, img_callback=img_callback)
 
+    # ------------------------------------------------------------------------------------------------ held regions
+    @staticmethod
+    def _check_hold(hold_mask, hold_x0, hold_noise, sampler=None):
+        """What a held-region call refuses before any draw; True when there is a hold."""
+        if hold_noise not in HOLD_NOISE:
+            raise ValueError(f"hold_noise must be one of {HOLD_NOISE}; got {hold_noise!r}")
+        if (hold_mask is None) != (hold_x0 is None):
+            raise ValueError("hold_mask and hold_x0 go together: got only " + ("hold_x0" if hold_mask is None else "hold_mask"))
+        if hold_mask is not None and sampler == "ddpm":
+            raise NotImplementedError('hold_mask / hold_x0 are defined for sampler="ddim" | "dpmpp_2m" | "dpmpp_2m_sde"; the ancestral '
+                                      "sampler takes the reference's mask / x0")
+        return hold_mask is not None
+
+    def _hold_operands(self, hold_mask, hold_x0, hold_noise, shape):
+        """None, or the hold of one sampler call: the mask (anything broadcastable to `shape`, fp32 in [0, 1], 1 = held) and the known
+        latent (the sampler's own space, scale_factor * E(x); batch 1 or the call's) expanded once to contiguous fp32 `shape` tensors on
+        the module's device.  The loops add the schedule's part (start row, tape layout)."""
+        if not self._check_hold(hold_mask, hold_x0, hold_noise):
+            return None
+        device, shape = self.betas.device, tuple(shape)
+        x0 = torch.as_tensor(hold_x0, device=device).float()
+        if x0.dim() != len(shape) or tuple(x0.shape[1:]) != shape[1:] or x0.shape[0] not in (1, shape[0]):
+            raise ValueError(f"hold_x0 must be {shape} or {(1,) + shape[1:]}; got {tuple(x0.shape)}")
+        mask = torch.as_tensor(hold_mask, device=device).float()
+        try:
+            mask = mask.broadcast_to(shape)
+        except RuntimeError:
+            raise ValueError(f"hold_mask {tuple(mask.shape)} does not broadcast to the latent batch {shape}") from None
+        return dict(x0=x0.expand(shape).contiguous(), mask=mask.contiguous(), fresh=hold_noise == "fresh")
+
+    def _hold_schedule(self, hold, table, guided, steps, visited, tape_own):
+        """The schedule's part of a hold: `table` (one row per visited step, in visiting order) widened by gamma = 0 when the run is not
+        guided and by the hold columns of schedule.make_hold_coefficients (`visited`: the grid indices in visiting order, None for
+        DDIM's); the start row; and whether the sampler's own step reads a tape entry (then the hold draw follows it, else it stands
+        in its place)."""
+        cols, start = make_hold_coefficients(self._alphas_cumprod_f64.astype(np.float32).astype(np.float64), steps, visited)
+        if not guided:
+            table = np.concatenate([table, np.zeros((len(table), 1), dtype=table.dtype)], axis=1)
+        hold.update(start=torch.tensor(start, dtype=torch.float32, device=self.betas.device), tape_own=bool(tape_own))
+        return np.concatenate([table, cols.astype(table.dtype)], axis=1)
+
+    @torch.no_grad()
+    def hold_from_frames(self, frames, first=0):
+        """(hold_mask, hold_x0) that hold target frames [first, first + k) to the pixel frames `frames` (B, k, H, W, C): hold_x0 is
+        scale_factor * first_stage_model.encode(frames).mode() on those frames and zero elsewhere (the VAE is frame-wise, so the hold
+        is exact per frame), hold_mask (1, T, 1, 1, 1) is 1 on them."""
+        T, k, first = int(self.latent_shape[0]), int(frames.shape[1]), int(first)
+        if frames.dim() != 5 or not (0 <= first and k >= 1 and first + k <= T):
+            raise ValueError(f"frames must be (B, k, H, W, C) with [first, first + k) inside the {T} target frames; got "
+                             f"{tuple(frames.shape)} at first={first}")
+        B = frames.shape[0]
+        post = self.first_stage_model.encode(self._to_frames(frames))
+        if isinstance(post, DiagonalGaussianDistribution):
+            post = post.mode()
+        elif hasattr(post, "latent_dist"):
+            post = post.latent_dist.mode()
+        z = self.scale_factor * self._from_frames(post, B).float()
+        x0 = torch.zeros(self.get_batch_latent_shape(B), dtype=torch.float32, device=z.device)
+        x0[:, first:first + k] = z
+        mask = torch.zeros((1, T, 1, 1, 1), dtype=torch.float32, device=z.device)
+        mask[:, first:first + k] = 1.0
+        return mask, x0
+
     @torch.no_grad()
     @_on_own_device
     def ddim_sample_loop(self, cond, shape, ddim_steps=50, eta=0.0, x_T=None, noise_tape=None, return_intermediates=False,
-                         ddim_discretize="uniform", use_alignment=False, alignment_kwargs=None, y=None):
+                         ddim_discretize="uniform", use_alignment=False, alignment_kwargs=None, y=None, hold_mask=None, hold_x0=None,
+                         hold_noise="fresh"):
         """DDIM over the reference's timestep subset (diffusion/utils.py:42-70).  NOT in the reference:
         z_prev = sqrt(a_prev) z0 + sqrt(1 - a_prev - sigma^2) eps + sigma n, denoiser queried at t = steps[i].
         use_alignment: knowledge-aligned DDIM, z_prev -= gamma_idx * alignment_fn(z_t, steps[idx], zc=cond, y=y,
         **alignment_kwargs) with gamma_idx from make_ddim_guidance_coefficients.  Noise tape / RNG: x_T, then tape[1 + k] (or a
-        device draw when eta > 0) for step k."""
+        device draw when eta > 0) for step k.
+        hold_mask / hold_x0 / hold_noise: a held region ("Held regions"); with "fresh" the tape is
+        [x_T, n_0, h_0, ..., n_{K-1}] (no tape: a device draw per h_k, after the step's own), with "fixed" the un-held run's."""
         B = shape[self.batch_axis]
+        hold = self._hold_operands(hold_mask, hold_x0, hold_noise, shape)
         if self.shorten_cond_schedule:
             raise NotImplementedError("shorten_cond_schedule (num_timesteps_cond > 1) is defined for the ancestral loop only")
         if not (1 <= int(ddim_steps) <= self.num_timesteps):
@@ -715,20 +827,27 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         if use_alignment:
             cols.append(make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), steps))
         # one row (a_t, a_prev, sigma[, gamma]) per step, rounded from fp64 to fp32 once
-        coefs = torch.tensor(np.stack(cols, axis=1), dtype=torch.float32, device=self.betas.device)
+        table, order = np.stack(cols, axis=1), list(reversed(range(len(steps))))
+        rows = order
+        if hold is not None:   # rows (a_t, a_prev, sigma, gamma, k_x, k_n) in visiting order; the step reads a tape entry of its own
+            table, rows = self._hold_schedule(hold, table[order], use_alignment, steps, None, True), list(range(len(order)))
+        coefs = torch.tensor(table, dtype=torch.float32, device=self.betas.device)
 
-        def epilogue(cur, eps, shift, ts, row, noise):
+        def epilogue(cur, eps, shift, ts, row, noise, hn=None):
             out = torch.empty_like(cur)
             coef = coefs[row].expand(B, coefs.shape[1]).contiguous()
             with L.on_device(cur):
-                if shift is None:
+                if hold is not None:
+                    L.ddim_step_held(cur, eps, noise, shift, hold["x0"], hold["mask"], cur if hn is None else hn, coef, out, B,
+                                     cur[0].numel())
+                elif shift is None:
                     L.ddim_step(cur, eps, noise if noise is not None else torch.zeros_like(cur), coef, out, B, cur[0].numel())
                 else:
                     L.ddim_step_guided(cur, eps, noise, shift, coef, out, B, cur[0].numel())
             return out
-        return self._run_sampler("ddim", cond, shape, x_T, noise_tape, [(int(steps[idx]), idx) for idx in reversed(range(len(steps)))],
+        return self._run_sampler("ddim", cond, shape, x_T, noise_tape, [(int(steps[idx]), row) for idx, row in zip(order, rows)],
                                  epilogue, coefs=coefs, draw="early" if eta > 0 else None, use_alignment=use_alignment, y=y,
-                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates)
+                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates, hold=hold)
 
     def _dpmpp_grid(self, steps, discretize, use_alignment):
         """What the two DPM-Solver++(2M) loops refuse, before any draw, then (alphas_cumprod as fp32 values in fp64, the grid)."""
@@ -751,62 +870,78 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
     @torch.no_grad()
     @_on_own_device
     def dpmpp_2m_sample_loop(self, cond, shape, steps=20, discretize="quad", lower_order_final=None, x_T=None, noise_tape=None,
-                             return_intermediates=False, use_alignment=False, alignment_kwargs=None, y=None):
+                             return_intermediates=False, use_alignment=False, alignment_kwargs=None, y=None, hold_mask=None,
+                             hold_x0=None, hold_noise="fresh"):
         """DPM-Solver++(2M), data prediction (not in the reference): a second-order multistep ODE solver, one denoiser
         call per step like DDIM at eta = 0, keeping the previous step's x0 (schedule.make_dpmpp_2m_coefficients has the rule).
         discretize: "quad" | "uniform" (make_ddim_timesteps) | "logsnr" (make_logsnr_timesteps); repeated grid points are dropped, so
         fewer than `steps` steps may run.  Deterministic: only x_T, else noise_tape[0], else one device draw, is consumed.
-        use_alignment: z_prev -= gamma_idx * alignment_fn(z_t, steps[idx], zc=cond, y=y, **alignment_kwargs), gamma_idx as guided DDIM."""
+        use_alignment: z_prev -= gamma_idx * alignment_fn(z_t, steps[idx], zc=cond, y=y, **alignment_kwargs), gamma_idx as guided DDIM.
+        hold_mask / hold_x0 / hold_noise: a held region ("Held regions"); "fresh" reads [x_T, h_0, ..., h_{K-2}] (a tape,
+        else device draws), "fixed" x_T alone."""
         B = shape[self.batch_axis]
+        hold = self._hold_operands(hold_mask, hold_x0, hold_noise, shape)
         ac, grid = self._dpmpp_grid(steps, discretize, use_alignment)
         table, visited = make_dpmpp_2m_coefficients(ac, grid, lower_order_final)
         if use_alignment:      # a dropped grid point has an empty J and gamma 0: the visited steps' J still partition {0..grid[-1]}
             gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), grid)
             table = np.concatenate([table, gamma[visited, None]], axis=1)
+        if hold is not None:   # rows (a_t, c_x, c_d, w, gamma, k_x, k_n); the step reads no tape entry: the hold draw stands in its place
+            table = self._hold_schedule(hold, table, use_alignment, grid, visited, False)
         # one row (a_t, c_x, c_d, w[, gamma]) per visited step, in visiting order
         coefs = torch.tensor(table, dtype=torch.float32, device=self.betas.device)
-        # the only draw of the run; the driver gets no tape, so a step-ordered (lazy) tape is read at index 0 and nowhere else
-        x_T = self._start_latent(x_T, noise_tape, shape, self.betas.device)
+        if hold is None or not hold["fresh"]:
+            # the only draw of the run; the driver gets no tape, so a step-ordered (lazy) tape is read at index 0 and nowhere else
+            x_T, noise_tape = self._start_latent(x_T, noise_tape, shape, self.betas.device), None
         hist = []              # aligned / eager mode: one x0 history for the whole batch, owned by this call
 
-        def epilogue(cur, eps, shift, ts, row, noise):
+        def epilogue(cur, eps, shift, ts, row, noise, hn=None):
             if not hist:
                 hist.append(torch.empty_like(cur))
             out = torch.empty_like(cur)
             coef = coefs[row].expand(B, coefs.shape[1]).contiguous()
             with L.on_device(cur):
-                if shift is None:
+                if hold is not None:
+                    L.dpmpp_2m_step_held(cur, eps, hist[0], shift, hold["x0"], hold["mask"], cur if hn is None else hn, coef, out, B,
+                                         cur[0].numel())
+                elif shift is None:
                     L.dpmpp_2m_step(cur, eps, hist[0], coef, out, B, cur[0].numel())
                 else:
                     L.dpmpp_2m_step_guided(cur, eps, hist[0], shift, coef, out, B, cur[0].numel())
             return out
-        return self._run_sampler("dpmpp", cond, shape, x_T, None, [(int(grid[idx]), k) for k, idx in enumerate(visited)], epilogue,
+        return self._run_sampler("dpmpp", cond, shape, x_T, noise_tape, [(int(grid[idx]), k) for k, idx in enumerate(visited)], epilogue,
                                  coefs=coefs, use_alignment=use_alignment, y=y, alignment_kwargs=alignment_kwargs,
-                                 return_intermediates=return_intermediates)
+                                 return_intermediates=return_intermediates, hold=hold)
 
     @torch.no_grad()
     @_on_own_device
     def dpmpp_2m_sde_sample_loop(self, cond, shape, steps=20, eta=1.0, discretize="quad", lower_order_final=None, x_T=None,
-                                 noise_tape=None, return_intermediates=False, use_alignment=False, alignment_kwargs=None, y=None):
+                                 noise_tape=None, return_intermediates=False, use_alignment=False, alignment_kwargs=None, y=None,
+                                 hold_mask=None, hold_x0=None, hold_noise="fresh"):
         """SDE-DPM-Solver++(2M) (not in the reference): dpmpp_2m_sample_loop's grid, visit list and x0 history with fresh
         noise at every step (schedule.make_dpmpp_2m_sde_coefficients has the rule).  eta = 1 is the stochastic solver, whose
         first-order member is DDIM at eta = 1; eta = 0 consumes x_T only and equals dpmpp_2m_sample_loop bit for bit.
         Noise tape / RNG as ddim_sample_loop: x_T, then tape[1 + k] (or one whole-batch device draw) for visited step k when eta > 0.
-        use_alignment: as dpmpp_2m_sample_loop."""
+        use_alignment: as dpmpp_2m_sample_loop.
+        hold_mask / hold_x0 / hold_noise: a held region ("Held regions"); with "fresh" the tape is
+        [x_T, n_0, h_0, ..., n_{K-1}] when eta > 0 and dpmpp_2m_sample_loop's [x_T, h_0, ..., h_{K-2}] at eta = 0."""
         B = shape[self.batch_axis]
+        hold = self._hold_operands(hold_mask, hold_x0, hold_noise, shape)
         ac, grid = self._dpmpp_grid(steps, discretize, use_alignment)
         table, visited = make_dpmpp_2m_sde_coefficients(ac, grid, eta, lower_order_final)
         if use_alignment:
             gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), grid)
             table = np.concatenate([table, gamma[visited, None]], axis=1)
+        stochastic = float(eta) > 0
+        if hold is not None:   # rows (a_t, c_x, c_d, w, c_n, gamma, k_x, k_n); the step reads a tape entry of its own when eta > 0
+            table = self._hold_schedule(hold, table, use_alignment, grid, visited, stochastic)
         # one row (a_t, c_x, c_d, w, c_n[, gamma]) per visited step, in visiting order
         coefs = torch.tensor(table, dtype=torch.float32, device=self.betas.device)
-        stochastic = float(eta) > 0
-        if not stochastic:     # as dpmpp_2m_sample_loop: draw 0 is the only draw, and the driver gets no tape
+        if not stochastic and (hold is None or not hold["fresh"]):     # as dpmpp_2m_sample_loop: draw 0 is the only draw, and the driver gets no tape
             x_T, noise_tape = self._start_latent(x_T, noise_tape, shape, self.betas.device), None
         hist = []              # aligned / eager mode: one x0 history for the whole batch, owned by this call
 
-        def epilogue(cur, eps, shift, ts, row, noise):
+        def epilogue(cur, eps, shift, ts, row, noise, hn=None):
             if not hist:
                 hist.append(torch.empty_like(cur))
             out = torch.empty_like(cur)
@@ -814,14 +949,17 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             if noise is None:  # eta = 0: every c_n is 0 and the kernel does not read the buffer
                 noise = cur
             with L.on_device(cur):
-                if shift is None:
+                if hold is not None:
+                    L.dpmpp_2m_sde_step_held(cur, eps, noise, hist[0], shift, hold["x0"], hold["mask"], cur if hn is None else hn, coef,
+                                             out, B, cur[0].numel())
+                elif shift is None:
                     L.dpmpp_2m_sde_step(cur, eps, noise, hist[0], coef, out, B, cur[0].numel())
                 else:
                     L.dpmpp_2m_sde_step_guided(cur, eps, noise, hist[0], shift, coef, out, B, cur[0].numel())
             return out
         return self._run_sampler("dpmpp_sde", cond, shape, x_T, noise_tape, [(int(grid[idx]), k) for k, idx in enumerate(visited)],
                                  epilogue, coefs=coefs, draw="early" if stochastic else None, use_alignment=use_alignment, y=y,
-                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates)
+                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates, hold=hold)
 
     @staticmethod
     def _pop_sampler_kwargs(kwargs):
@@ -848,14 +986,19 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
 
     def _sample_latent(self, zc, shape, y, *, sampler="ddpm", ddim_steps=None, eta=0.0, steps=None, discretize="quad",
                        lower_order_final=None, timesteps=None, x_T=None, noise_tape=None, use_alignment=False, alignment_kwargs=None,
-                       return_intermediates=False, mask=None, x0=None, verbose=False):
-        """`sample`'s sampler dispatch on a latent context: the loop's output, undecoded (rollout.rollout_sample calls it per segment)."""
+                       return_intermediates=False, mask=None, x0=None, verbose=False, hold_mask=None, hold_x0=None, hold_noise="fresh"):
+        """`sample`'s sampler dispatch on a latent context: the loop's output, undecoded (rollout.rollout_sample calls it per segment).
+        mask / x0 keep the reference's meaning (ancestral loop only); hold_mask / hold_x0 / hold_noise are the engine's own held regions
+        of the three fast samplers ("Held regions")."""
+        fast = sampler in ("ddim", "dpmpp_2m", "dpmpp_2m_sde")
+        self._check_hold(hold_mask, hold_x0, hold_noise, sampler if fast else "ddpm")
+        hold = dict(hold_mask=hold_mask, hold_x0=hold_x0, hold_noise=hold_noise)
         if sampler == "ddim":
             if mask is not None:
                 raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
             return self.ddim_sample_loop(zc, shape, ddim_steps=50 if ddim_steps is None else ddim_steps, eta=eta, x_T=x_T,
                                          noise_tape=noise_tape, return_intermediates=return_intermediates,
-                                         use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y)
+                                         use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y, **hold)
         if sampler == "dpmpp_2m":
             if mask is not None:
                 raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
@@ -865,7 +1008,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                 steps = 20 if ddim_steps is None else ddim_steps
             return self.dpmpp_2m_sample_loop(zc, shape, steps=steps, discretize=discretize, lower_order_final=lower_order_final,
                                              x_T=x_T, noise_tape=noise_tape, return_intermediates=return_intermediates,
-                                             use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y)
+                                             use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y, **hold)
         if sampler == "dpmpp_2m_sde":
             if mask is not None:
                 raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
@@ -874,7 +1017,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             return self.dpmpp_2m_sde_sample_loop(zc, shape, steps=steps, eta=eta, discretize=discretize,
                                                  lower_order_final=lower_order_final, x_T=x_T, noise_tape=noise_tape,
                                                  return_intermediates=return_intermediates, use_alignment=use_alignment,
-                                                 alignment_kwargs=alignment_kwargs, y=y)
+                                                 alignment_kwargs=alignment_kwargs, y=y, **hold)
         return self.p_sample_loop(cond=zc, shape=shape, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
                                   return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
                                   mask=mask, x0=x0, noise_tape=noise_tape)
@@ -882,11 +1025,16 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
     @torch.no_grad()
     @_on_own_device
     def sample(self, cond, batch_size=16, use_alignment=False, alignment_kwargs=None, return_intermediates=False, x_T=None,
-               verbose=False, timesteps=None, mask=None, x0=None, shape=None, return_decoded=True, **kwargs):
+               verbose=False, timesteps=None, mask=None, x0=None, shape=None, return_decoded=True, hold_mask=None, hold_x0=None,
+               hold_noise="fresh", **kwargs):
         """latent_diffusion.py:686-724.  Extra keywords (new API, consumed from **kwargs): sampler="ddpm"|"ddim"|"dpmpp_2m"|
         "dpmpp_2m_sde", ddim_steps=50, eta=0.0, noise_tape=[x_T, n_1, ...]; with "dpmpp_2m" and "dpmpp_2m_sde": steps=20 (`ddim_steps` is
-        accepted as an alias), discretize="quad"|"uniform"|"logsnr", lower_order_final=None; "dpmpp_2m_sde" defaults to eta=1.0."""
+        accepted as an alias), discretize="quad"|"uniform"|"logsnr", lower_order_final=None; "dpmpp_2m_sde" defaults to eta=1.0.
+        hold_mask / hold_x0 / hold_noise="fresh"|"fixed": a held region of the three fast samplers (DESIGN.md §7, "Held regions";
+        hold_from_frames makes the pair from pixel frames); mask / x0 keep the reference's meaning on the ancestral loop."""
         sampler_kwargs = self._pop_sampler_kwargs(kwargs)
+        fast = sampler_kwargs["sampler"] in ("ddim", "dpmpp_2m", "dpmpp_2m_sde")     # refused before the context is encoded
+        self._check_hold(hold_mask, hold_x0, hold_noise, sampler_kwargs["sampler"] if fast else "ddpm")
         noise_tape = kwargs.pop("noise_tape", None)
         if use_alignment:
             assert self.alignment_fn is not None, "Alignment function not set."
@@ -895,7 +1043,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         zc, y = self._latent_context(cond, batch_size)
         output = self._sample_latent(zc, shape, y, timesteps=timesteps, x_T=x_T, noise_tape=noise_tape, use_alignment=use_alignment,
                                      alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates, mask=mask, x0=x0,
-                                     verbose=verbose, **sampler_kwargs)
+                                     verbose=verbose, hold_mask=hold_mask, hold_x0=hold_x0, hold_noise=hold_noise, **sampler_kwargs)
         if return_decoded:
             if return_intermediates:
                 samples, inter = output

@@ -24,6 +24,7 @@ from .ensemble import _LazyTape, member_noise_fn, sample_ensemble
 from .tiled import TiledLatentDiffusion
 
 RECONDITION = ("latent", "pixel")
+OVERLAP = ("discard", "hold")
 
 
 def _int(name, v):
@@ -88,7 +89,7 @@ def _plan_for(ldm, cond, horizon, stride):
 
 @torch.no_grad()
 def rollout_sample(ldm, cond, horizon, stride=None, recondition="latent", batch_size=16, return_decoded=True, noise_tape=None, x_T=None,
-                   use_alignment=False, alignment_kwargs=None, **sampler_kwargs):
+                   use_alignment=False, alignment_kwargs=None, overlap="discard", **sampler_kwargs):
     """`horizon` forecast frames from a ``LatentDiffusion`` or ``TiledLatentDiffusion`` whose checkpoint forecasts latent_shape[0] of them.
 
     cond, batch_size, return_decoded, use_alignment and the sampler keywords (sampler, ddim_steps, eta, steps, discretize,
@@ -99,10 +100,21 @@ def rollout_sample(ldm, cond, horizon, stride=None, recondition="latent", batch_
     pd_context_advance launch per segment, the VAE decodes once at the end (never with return_decoded=False), and the alignment function
     sees the caller's pixel context y in segment 0 and y=None afterwards.  recondition="pixel": the next PIXEL context is
     [y ; decode(z)][stride : stride + in_len], encoded by the module's cond_stage_forward (needs cond_stage_model="__is_first_stage__").
+    overlap="discard": the out_len - stride frames that segment j + 1 forecasts again are forecast freely and segment j's are dropped.
+    overlap="hold" (stride < out_len; the three fast samplers): segment j >= 1 runs with its first out_len - stride frames HELD to the
+    latent frames z_{j-1}[:, stride:] (``sample``'s hold_mask / hold_x0, DESIGN.md §7 "Held regions"; `hold_noise` is taken here), so
+    it out-paints segment j - 1 in time and consecutive segments agree where they meet.  The held frames are latents and pass
+    through no VAE, also with recondition="pixel".
     Returns (B, horizon, ...): decoded frames, or latents with return_decoded=False."""
     kw = dict(sampler_kwargs)
     if kw.pop("mask", None) is not None or kw.pop("x0", None) is not None:
         raise NotImplementedError("inpainting (mask / x0) is not defined for a rolling forecast")
+    if kw.pop("hold_mask", None) is not None or kw.pop("hold_x0", None) is not None:
+        raise NotImplementedError('hold_mask / hold_x0 are not defined for a rolling forecast (which segment would they hold?); '
+                                  'overlap="hold" holds the frames two segments share')
+    hold_noise = kw.pop("hold_noise", "fresh")
+    if overlap not in OVERLAP:
+        raise ValueError(f"overlap must be one of {OVERLAP}; got {overlap!r}")
     if kw.pop("return_intermediates", False):
         raise NotImplementedError("return_intermediates=True is not defined for a rolling forecast")
     if recondition not in RECONDITION:
@@ -117,18 +129,34 @@ def rollout_sample(ldm, cond, horizon, stride=None, recondition="latent", batch_
         raise ValueError('recondition="pixel" encodes the decoded forecast as the next context: it needs cond_stage_model="__is_first_stage__"')
     plan, y0 = _plan_for(ldm, cond, horizon, stride)
     n, s = plan.segments, plan.stride
+    if overlap == "hold":
+        if s == plan.out_len:
+            raise ValueError(f'overlap="hold" needs stride < out_len = {plan.out_len}: with stride == out_len no frame is forecast twice')
+        ldm._check_hold(None, None, hold_noise)
     tapes, x_Ts = _per_segment("noise_tape", noise_tape, n), _per_segment("x_T", x_T, n)
     aks = _per_segment("alignment_kwargs", alignment_kwargs, n, single=(dict,))
     loop_kw = dict(ldm._pop_sampler_kwargs(kw), timesteps=kw.pop("timesteps", None), verbose=kw.pop("verbose", False))
     if kw:
         raise TypeError(f"rollout_sample got unexpected keyword arguments {sorted(kw)}")
+    if overlap == "hold" and loop_kw["sampler"] not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde"):
+        raise NotImplementedError('overlap="hold" is defined for sampler="ddim" | "dpmpp_2m" | "dpmpp_2m_sde" (held regions)')
     B = int(batch_size)
     shape = ldm.get_batch_latent_shape(batch_size=B)
     dev = ldm.betas.device
     with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-        def run(zc, y, j):
+        held = None
+        if overlap == "hold":                     # the frames a segment shares with the one before it
+            held = torch.zeros((1, plan.out_len) + (1,) * (len(shape) - 2), dtype=torch.float32, device=dev)
+            held[:, :plan.out_len - s] = 1.0
+
+        def run(zc, y, j, prev=None):
+            hold = {}
+            if held is not None and prev is not None:
+                x0 = torch.zeros(shape, dtype=torch.float32, device=prev.device)
+                x0[:, :plan.out_len - s].copy_(prev[:, s:])
+                hold = dict(hold_mask=held, hold_x0=x0, hold_noise=hold_noise)
             return ldm._sample_latent(zc, shape, y, x_T=x_Ts[j], noise_tape=tapes[j], use_alignment=use_alignment, alignment_kwargs=aks[j],
-                                      **loop_kw)
+                                      **hold, **loop_kw)
         if recondition == "pixel" and n > 1:
             return _pixel_chain(ldm, cond, plan, B, run, return_decoded)
         zc, y = ldm._latent_context(cond, B)
@@ -150,7 +178,7 @@ def rollout_sample(ldm, cond, horizon, stride=None, recondition="latent", batch_
             with L.on_device(z):
                 L.context_advance(ctx, z.contiguous().float(), origins, nxt, s, z_scale, forecast=out, f_off=plan.starts[j], f_cnt=plan.keep[j])
             ctx = nxt
-            z = run(ctx if tiled else ctx[:, 0], None, j + 1)
+            z = run(ctx if tiled else ctx[:, 0], None, j + 1, z)
         out[:, plan.starts[-1]:].copy_(z[:, :plan.keep[-1]])
         return ldm.decode_first_stage(out) if return_decoded else out
 
@@ -159,11 +187,11 @@ def _pixel_chain(ldm, cond, plan, B, run, return_decoded):
     """recondition="pixel": every segment is `sample`'s run on the pixel context [y ; decode(z)][stride : stride + in_len]; the kept pixel
     frames are those decoded for the feedback (the last segment is decoded only when pixels are returned)."""
     y =(cond.get("y") if isinstance(cond, dict) else cond)[:B]
-    kept = []
+    kept, z = [], None
     for j in range(plan.segments):
         cj = dict(cond, y=y) if isinstance(cond, dict) else y
         zc, yj = ldm._latent_context(cj, B)
-        z = run(zc, yj, j)
+        z = run(zc, yj, j, z)
         last = j == plan.segments - 1
         x = ldm.decode_first_stage(z) if return_decoded or not last else None
         kept.append((x if return_decoded else z)[:, :plan.keep[j]])

@@ -149,6 +149,23 @@ def make_dpmpp_2m_sde_coefficients(alphacums, timesteps, eta, lower_order_final=
     return np.stack([a, c_x, c_d, w, c_n], axis=1).astype(np.float32), visited
 
 
+def make_hold_coefficients(alphacums, timesteps, visited=None):
+    """The hold columns of a held-region run ("Held regions") on the grid of make_ddim_sampling_parameters.  `visited`:
+    the grid indices in visiting order (default: every grid point from the last to the first, DDIM's order; the 2M loops pass the
+    visit list of make_dpmpp_2m_coefficients).  After visited step k the held part is the known latent at the level the denoiser
+    sees next: u_k = a_prev of step k, and u = 1 after the last step, which writes the known latent itself.
+    Returns (cols, start): cols[k] = (sqrt(u_k), sqrt(1 - u_k)), the last row exactly (1, 0); start = (sqrt(a_0), sqrt(1 - a_0)) with
+    a_0 the level the first step reads.  fp64 from the alphacums as given, rounded to fp32 once."""
+    _, a, a_prev = make_ddim_sampling_parameters(np.asarray(alphacums, dtype=np.float64), timesteps, 0.0)
+    visited = np.arange(len(a) - 1, -1, -1) if visited is None else np.asarray(visited, dtype=np.int64)
+    if len(visited) == 0:
+        raise ValueError("a held run needs at least one visited step")
+    u = np.append(a_prev[visited[:-1]], 1.0)
+    a0 = a[visited[0]]
+    return (np.stack([np.sqrt(u), np.sqrt(1.0 - u)], axis=1).astype(np.float32),
+            np.asarray([np.sqrt(a0), np.sqrt(1.0 - a0)]).astype(np.float32))
+
+
 def make_ddim_guidance_coefficients(posterior_log_variance_clipped, ddim_timesteps) -> np.ndarray:
     """gamma per DDIM step of the knowledge-aligned DDIM sampler: step idx moves from t = steps[idx] to the alpha of
     steps[idx-1] and skips the DDPM timesteps J_idx = {steps[idx-1] + 1, ..., steps[idx]} ({0, ..., steps[0]} for idx = 0); it

@@ -277,6 +277,11 @@ class TiledLatentDiffusion(LatentDiffusion):
         self._check_latent_context(cond)
         return super().sample(cond, *args, **kwargs)
 
+    def hold_from_frames(self, frames, first=0):
+        """Held regions (hold_mask / hold_x0, canvas-shaped) pass straight through to the step on the canvas; encoding pixel frames
+        into a canvas latent is not defined here (the tiled VAE encodes context tiles window by window, without blending)."""
+        raise NotImplementedError("hold_from_frames is not defined on a canvas: pass a canvas-shaped latent as hold_x0")
+
     def _check_latent_context(self, cond):
         """Without a condition stage the context is a latent canvas (also checked by rollout.rollout_sample)."""
         if self.cond_stage_model is None:
