@@ -565,100 +565,72 @@ def ddpm_step(zt, eps, noise, mean_shift, t, coef, T, out, B, per_sample, temper
                               per_sample, temperature, 1 if clip_denoised else 0, stream_ptr()), "pd_ddpm_step")
 
 
+def _step(fn, B, per_sample, width, nullable=(), **operands):
+    """Check and launch pd_<fn>(*operands, B, per_sample, stream), the form of every sampler-step entry point: `operands` are its
+    pointer arguments by name, in its order.  Each is a contiguous fp32 device tensor of >= B * per_sample elements, the coefficient
+    rows (the operand named coef...) of >= B * width; only the names in `nullable` may be None."""
+    for name, x in operands.items():
+        need = B * (width if name.startswith("coef") else per_sample)
+        if x is None:
+            if name not in nullable:
+                raise PrediffHipError(f"{fn}: {name} must not be None")
+        elif x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.numel() < need:
+            raise PrediffHipError(f"{fn}: {name} must be a contiguous fp32 device tensor of >= {need} elements")
+    _check(getattr(lib(), "pd_" + fn)(*map(ptr, operands.values()), B, per_sample, stream_ptr()), "pd_" + fn)
+
+
 def ddim_step(zt, eps, noise, coef, out, B, per_sample):
-    _check(lib().pd_ddim_step(ptr(zt), ptr(eps), ptr(noise), ptr(coef), ptr(out), B, per_sample, stream_ptr()),
-           "pd_ddim_step")
+    """One DDIM step (coef rows: a_t, a_prev, sigma); `noise` may be None (eta = 0)."""
+    _step("ddim_step", B, per_sample, 3, ("noise",), zt=zt, eps=eps, noise=noise, coef=coef, out=out)
 
 
 def ddim_step_guided(zt, eps, noise, shift, coef4, out, B, per_sample):
     """pd_ddim_step minus gamma * shift (coef4 rows: a_t, a_prev, sigma, gamma); `noise` may be None (eta = 0)."""
-    n = B * per_sample
-    for name, x, need in (("zt", zt, n), ("eps", eps, n), ("noise", noise, n), ("shift", shift, n), ("coef4", coef4, 4 * B), ("out", out, n)):
-        if x is not None and (x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < need):
-            raise PrediffHipError(f"ddim_step_guided: {name} must be a contiguous fp32 tensor of >= {need} elements")
-    _check(lib().pd_ddim_step_guided(ptr(zt), ptr(eps), ptr(noise), ptr(shift), ptr(coef4), ptr(out), B, per_sample, stream_ptr()),
-           "pd_ddim_step_guided")
-
-
-def _check_step_operands(fn, operands):
-    for name, x, need in operands:
-        if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.numel() < need:
-            raise PrediffHipError(f"{fn}: {name} must be a contiguous fp32 device tensor of >= {need} elements")
+    _step("ddim_step_guided", B, per_sample, 4, ("noise",), zt=zt, eps=eps, noise=noise, shift=shift, coef4=coef4, out=out)
 
 
 def dpmpp_2m_step(zt, eps, hist, coef4, out, B, per_sample):
     """One DPM-Solver++(2M) step (coef4 rows: a_t, c_x, c_d, w); `hist` (the previous x0) is updated in place."""
-    n = B * per_sample
-    _check_step_operands("dpmpp_2m_step", (("zt", zt, n), ("eps", eps, n), ("hist", hist, n), ("coef4", coef4, 4 * B), ("out", out, n)))
-    _check(lib().pd_dpmpp_2m_step(ptr(zt), ptr(eps), ptr(hist), ptr(coef4), ptr(out), B, per_sample, stream_ptr()), "pd_dpmpp_2m_step")
+    _step("dpmpp_2m_step", B, per_sample, 4, zt=zt, eps=eps, hist=hist, coef4=coef4, out=out)
 
 
 def dpmpp_2m_step_guided(zt, eps, hist, shift, coef5, out, B, per_sample):
     """pd_dpmpp_2m_step minus gamma * shift (coef5 rows: a_t, c_x, c_d, w, gamma)."""
-    n = B * per_sample
-    _check_step_operands("dpmpp_2m_step_guided", (("zt", zt, n), ("eps", eps, n), ("hist", hist, n), ("shift", shift, n),
-                                                  ("coef5", coef5, 5 * B), ("out", out, n)))
-    _check(lib().pd_dpmpp_2m_step_guided(ptr(zt), ptr(eps), ptr(hist), ptr(shift), ptr(coef5), ptr(out), B, per_sample, stream_ptr()),
-           "pd_dpmpp_2m_step_guided")
+    _step("dpmpp_2m_step_guided", B, per_sample, 5, zt=zt, eps=eps, hist=hist, shift=shift, coef5=coef5, out=out)
 
 
 def dpmpp_2m_sde_step(zt, eps, noise, hist, coef5, out, B, per_sample):
     """One SDE-DPM-Solver++(2M) step (coef5 rows: a_t, c_x, c_d, w, c_n); `noise` is read only where c_n != 0, `hist` is updated in place."""
-    n = B * per_sample
-    _check_step_operands("dpmpp_2m_sde_step", (("zt", zt, n), ("eps", eps, n), ("noise", noise, n), ("hist", hist, n),
-                                               ("coef5", coef5, 5 * B), ("out", out, n)))
-    _check(lib().pd_dpmpp_2m_sde_step(ptr(zt), ptr(eps), ptr(noise), ptr(hist), ptr(coef5), ptr(out), B, per_sample, stream_ptr()),
-           "pd_dpmpp_2m_sde_step")
+    _step("dpmpp_2m_sde_step", B, per_sample, 5, zt=zt, eps=eps, noise=noise, hist=hist, coef5=coef5, out=out)
 
 
 def dpmpp_2m_sde_step_guided(zt, eps, noise, hist, shift, coef6, out, B, per_sample):
     """pd_dpmpp_2m_sde_step minus gamma * shift (coef6 rows: a_t, c_x, c_d, w, c_n, gamma)."""
-    n = B * per_sample
-    _check_step_operands("dpmpp_2m_sde_step_guided", (("zt", zt, n), ("eps", eps, n), ("noise", noise, n), ("hist", hist, n),
-                                                      ("shift", shift, n), ("coef6", coef6, 6 * B), ("out", out, n)))
-    _check(lib().pd_dpmpp_2m_sde_step_guided(ptr(zt), ptr(eps), ptr(noise), ptr(hist), ptr(shift), ptr(coef6), ptr(out), B, per_sample,
-                                             stream_ptr()), "pd_dpmpp_2m_sde_step_guided")
-
-
-def _held_operands(fn, B, per_sample, width, coef, named):
-    """Operand check of the held step kernels: every given tensor covers B * per_sample elements, the rows B * width; `shift` and DDIM's
-    `noise` may be None."""
-    n = B * per_sample
-    _check_step_operands(fn, tuple((name, x, n) for name, x in named if x is not None) + ((f"coef{width}", coef, width * B),))
-    for name, x in named:
-        if x is None and name not in ("shift", "noise"):
-            raise PrediffHipError(f"{fn}: {name} must not be None")
+    _step("dpmpp_2m_sde_step_guided", B, per_sample, 6, zt=zt, eps=eps, noise=noise, hist=hist, shift=shift, coef6=coef6, out=out)
 
 
 def ddim_step_held(zt, eps, noise, shift, hold_x0, hold_mask, hold_noise, coef6, out, B, per_sample):
     """pd_ddim_step[_guided] and the hold in one launch (coef6 rows: a_t, a_prev, sigma, gamma, k_x, k_n); `noise` may be None (eta = 0),
     `shift` None is the un-guided step; `hold_noise` is read only where k_n != 0."""
-    _held_operands("ddim_step_held", B, per_sample, 6, coef6, (("zt", zt), ("eps", eps), ("noise", noise), ("shift", shift),
-                   ("hold_x0", hold_x0), ("hold_mask", hold_mask), ("hold_noise", hold_noise), ("out", out)))
-    _check(lib().pd_ddim_step_held(ptr(zt), ptr(eps), ptr(noise), ptr(shift), ptr(hold_x0), ptr(hold_mask), ptr(hold_noise), ptr(coef6),
-                                   ptr(out), B, per_sample, stream_ptr()), "pd_ddim_step_held")
+    _step("ddim_step_held", B, per_sample, 6, ("noise", "shift"), zt=zt, eps=eps, noise=noise, shift=shift, hold_x0=hold_x0,
+          hold_mask=hold_mask, hold_noise=hold_noise, coef6=coef6, out=out)
 
 
 def dpmpp_2m_step_held(zt, eps, hist, shift, hold_x0, hold_mask, hold_noise, coef7, out, B, per_sample):
     """pd_dpmpp_2m_step[_guided] and the hold in one launch (coef7 rows: a_t, c_x, c_d, w, gamma, k_x, k_n)."""
-    _held_operands("dpmpp_2m_step_held", B, per_sample, 7, coef7, (("zt", zt), ("eps", eps), ("hist", hist), ("shift", shift),
-                   ("hold_x0", hold_x0), ("hold_mask", hold_mask), ("hold_noise", hold_noise), ("out", out)))
-    _check(lib().pd_dpmpp_2m_step_held(ptr(zt), ptr(eps), ptr(hist), ptr(shift), ptr(hold_x0), ptr(hold_mask), ptr(hold_noise), ptr(coef7),
-                                       ptr(out), B, per_sample, stream_ptr()), "pd_dpmpp_2m_step_held")
+    _step("dpmpp_2m_step_held", B, per_sample, 7, ("shift",), zt=zt, eps=eps, hist=hist, shift=shift, hold_x0=hold_x0, hold_mask=hold_mask,
+          hold_noise=hold_noise, coef7=coef7, out=out)
 
 
 def dpmpp_2m_sde_step_held(zt, eps, noise, hist, shift, hold_x0, hold_mask, hold_noise, coef8, out, B, per_sample):
     """pd_dpmpp_2m_sde_step[_guided] and the hold in one launch (coef8 rows: a_t, c_x, c_d, w, c_n, gamma, k_x, k_n)."""
-    _held_operands("dpmpp_2m_sde_step_held", B, per_sample, 8, coef8, (("zt", zt), ("eps", eps), ("sde noise", noise), ("hist", hist),
-                   ("shift", shift), ("hold_x0", hold_x0), ("hold_mask", hold_mask), ("hold_noise", hold_noise), ("out", out)))
-    _check(lib().pd_dpmpp_2m_sde_step_held(ptr(zt), ptr(eps), ptr(noise), ptr(hist), ptr(shift), ptr(hold_x0), ptr(hold_mask),
-                                           ptr(hold_noise), ptr(coef8), ptr(out), B, per_sample, stream_ptr()), "pd_dpmpp_2m_sde_step_held")
+    _step("dpmpp_2m_sde_step_held", B, per_sample, 8, ("shift",), zt=zt, eps=eps, noise=noise, hist=hist, shift=shift, hold_x0=hold_x0,
+          hold_mask=hold_mask, hold_noise=hold_noise, coef8=coef8, out=out)
 
 
 def hold_blend(z, x0, mask, noise, coef2, out, B, per_sample):
     """The start rule of a held run: out = mask-select of z and k_x x0 + k_n noise (coef2 rows: k_x, k_n); `out` may be `z`."""
-    _held_operands("hold_blend", B, per_sample, 2, coef2, (("z", z), ("x0", x0), ("mask", mask), ("hold noise", noise), ("out", out)))
-    _check(lib().pd_hold_blend(ptr(z), ptr(x0), ptr(mask), ptr(noise), ptr(coef2), ptr(out), B, per_sample, stream_ptr()), "pd_hold_blend")
+    _step("hold_blend", B, per_sample, 2, z=z, x0=x0, mask=mask, noise=noise, coef2=coef2, out=out)
 
 
 _origin_tables = {}      # (table bytes, canvas, window, device, covering) -> the checked device copy

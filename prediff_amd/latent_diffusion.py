@@ -4,9 +4,9 @@ p_sample :598-631, p_mean_variance :568-590, q_posterior :559-566, predict_start
 aligned_mean :592-596, apply_model :440-445, encode/decode_first_stage :423-438, cond-stage wrapper :361-380).
 
 Same constructor keywords and call conventions; what changes:
-  * one denoising step = denoiser forward (HIP kernels) + ONE fused step-epilogue kernel (pd_ddpm_step / pd_ddim_step /
-    pd_dpmpp_2m_step / pd_dpmpp_2m_sde_step)
-    instead of ~10 elementwise launches; the per-step schedule scalars are gathered on the device from t;
+  * one denoising step = denoiser forward (HIP kernels) + ONE fused step-epilogue kernel instead of ~10 elementwise launches:
+    pd_ddpm_step, which gathers the per-step schedule scalars on the device from t, or a fast sampler's pd_<stem>, pd_<stem>_guided or
+    pd_<stem>_held (stem ddim_step / dpmpp_2m_step / dpmpp_2m_sde_step), picked by step_rules.launch_step from the sampler's StepRule;
   * the step (denoiser + epilogue) is captured once into a HIP graph per (batch, sampler) and replayed: the host loop
     only refreshes t / noise, so small batches are not launch-bound;
   * a DDIM sampler exists (the reference ships only the two schedule helpers): ``sample(...,
@@ -30,13 +30,10 @@ from . import _lib as L
 from .distributions import DiagonalGaussianDistribution
 from .ema import LitEma
 from .loss_eval import LossEvaluationMixin
-from .schedule import (make_beta_schedule, make_ddim_guidance_coefficients, make_ddim_sampling_parameters, make_ddim_timesteps,
-                       make_dpmpp_2m_coefficients, make_dpmpp_2m_sde_coefficients, make_hold_coefficients, make_logsnr_timesteps,
-                       schedule_tables)
+from .schedule import make_beta_schedule, make_ddim_guidance_coefficients, make_hold_coefficients, schedule_tables
+from .step_rules import DDIM, DPMPP_2M, DPMPP_2M_SDE, GRAPH_KINDS, RULES, launch_step
 
 HOLD_NOISE = ("fresh", "fixed")
-# fp32 columns of a step's coefficient row per graph kind; the "_held" kinds carry (gamma, k_x, k_n) behind the un-held row
-_COEF_WIDTH = {"dpmpp": 4, "dpmpp_sde": 5, "ddim_held": 6, "dpmpp_held": 7, "dpmpp_sde_held": 8}
 
 
 def parse_layout_shape(layout: str) -> Dict[str, int]:
@@ -408,11 +405,17 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
     # ------------------------------------------------------------------------------------------------ graph-captured step
     def _graph_step(self, kind, B, zc, device, lane=0):
         """Capture (denoiser forward + step epilogue) once per (lane, kind, B) into a HIP graph; returns the static buffers.
+        kind: "eps" (the denoiser alone), "ddpm", a fast sampler's graph kind (step_rules.GRAPH_KINDS: its un-held step) or
+        (rule, held) as the step driver passes it.
         `lane` selects the denoiser's workspace set, so graphs of different lanes may replay concurrently on different streams."""
+        rule, held = kind if isinstance(kind, tuple) else (GRAPH_KINDS.get(kind), False)
         net = self.torch_nn_module
         if hasattr(net, "_ensure_packed"):
             net._ensure_packed(device)       # a weight update re-packs -> new operand buffers -> the old graph is stale
-        key = (kind, B, str(device), tuple(zc.shape), getattr(net, "_pack_generation", None), self.clip_denoised)
+        if rule is None and kind not in ("eps", "ddpm"):
+            raise ValueError(f"unknown graph kind {kind!r}")
+        key = (kind if rule is None else (rule, held), B, str(device), tuple(zc.shape), getattr(net, "_pack_generation", None),
+               self.clip_denoised)
         g = self._graphs.get(lane)
         if g is not None and g[0] == key:
             g[1]["zc"].copy_(zc)
@@ -420,35 +423,24 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         shape = self.get_batch_latent_shape(B)
         st = dict(z=torch.zeros(shape, device=device), noise=torch.zeros(shape, device=device),
                   t=torch.zeros(B, dtype=torch.int64, device=device), out=torch.zeros(shape, device=device),
-                  coef=torch.zeros(B, _COEF_WIDTH.get(kind, 3), device=device), zc=zc.detach().clone().float().contiguous())
-        if kind.startswith("dpmpp"):         # the previous step's x0; every loop's first step has w = 0 and does not read it
+                  coef=torch.zeros(B, 3 if rule is None else rule.row_width(False, held), device=device),
+                  zc=zc.detach().clone().float().contiguous())
+        if rule is not None and rule.hist:   # the previous step's x0; every loop's first step has w = 0 and does not read it
             st["hist"] = torch.zeros(shape, device=device)
-        held = kind.endswith("_held")        # held-region run: the known latent, the mask and the hold's noise are static inputs too
-        if held:
+        if held:                             # held-region run: the known latent, the mask and the hold's noise are static inputs too
             st.update({k: torch.zeros(shape, device=device) for k in ("hold_x0", "hold_mask", "hold_noise")})
 
         def body():
             if hasattr(net, "_ws_slot"):
                 net._ws_slot = lane
             eps = self.apply_model(st["z"], st["t"], st["zc"])
-            if held:
-                hold = (st["hold_x0"], st["hold_mask"], st["hold_noise"], st["coef"], st["out"], B, st["z"][0].numel())
             if kind == "eps":            # denoiser only: the step epilogue needs the alignment shift, computed outside the graph
                 st["out"].copy_(eps)
             elif kind == "ddpm":
                 self._ddpm_update(st["z"], eps, st["noise"], None, st["t"], 1.0, self.clip_denoised, out=st["out"])
-            elif kind == "ddim_held":
-                L.ddim_step_held(st["z"], eps, st["noise"], None, *hold)
-            elif kind == "dpmpp_held":
-                L.dpmpp_2m_step_held(st["z"], eps, st["hist"], None, *hold)
-            elif kind == "dpmpp_sde_held":
-                L.dpmpp_2m_sde_step_held(st["z"], eps, st["noise"], st["hist"], None, *hold)
-            elif kind == "dpmpp":
-                L.dpmpp_2m_step(st["z"], eps, st["hist"], st["coef"], st["out"], B, st["z"][0].numel())
-            elif kind == "dpmpp_sde":
-                L.dpmpp_2m_sde_step(st["z"], eps, st["noise"], st["hist"], st["coef"], st["out"], B, st["z"][0].numel())
             else:
-                L.ddim_step(st["z"], eps, st["noise"], st["coef"], st["out"], B, st["z"][0].numel())
+                launch_step(rule, st["z"], eps, st["noise"], st.get("hist"), None,
+                            (st["hold_x0"], st["hold_mask"], st["hold_noise"]) if held else None, st["coef"], st["out"])
         torch.cuda.synchronize(device)          # no other lane is mid-replay while this one warms up / captures
         side = torch.cuda.Stream(device=device)
         side.wait_stream(torch.cuda.current_stream(device))
@@ -596,23 +588,24 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             return noise_tape[1 + per_step * k + slot].to(device).contiguous()
         return draw() if draw is not None else None
 
-    def _run_sampler(self, kind, cond, shape, x_T, noise_tape, visits, epilogue, coefs=None, draw=None, eager=None,
+    def _run_sampler(self, rule, cond, shape, x_T, noise_tape, visits, coefs=None, draw=None, epilogue=None, eager=None,
                      use_alignment=False, y=None, alignment_kwargs=None, return_intermediates=False, log_every_t=1, mask=None,
                      x0=None, callback=None, img_callback=None, hold=None):
-        """The step loop of every sampler.  One of four modes is chosen once per call:
-          lanes   -- one `kind` graph per equal sub-batch, each replayed on its own stream (no per-step hooks; see _lanes);
-          graph   -- one `kind` graph replayed on the caller's stream;
-          aligned -- use_alignment: denoiser-only ("eps") graphs next to the guidance on the whole batch, then `epilogue`;
-          eager   -- no graphs: `eager(img, ts, noise, cond)` (the ancestral loop's p_sample), else denoiser, guidance, `epilogue`.
+        """The step loop of every sampler.  rule: the fast sampler's StepRule, whose step is one step_rules.launch_step; None is the
+        ancestral loop (graph kind "ddpm"), which brings its own `epilogue`.  One of four modes is chosen once per call:
+          lanes   -- one step graph per equal sub-batch, each replayed on its own stream (no per-step hooks; see _lanes);
+          graph   -- one step graph replayed on the caller's stream;
+          aligned -- use_alignment: denoiser-only ("eps") graphs next to the guidance on the whole batch, then the step;
+          eager   -- no graphs: `eager(img, ts, noise, cond)` (the ancestral loop's p_sample), else denoiser, guidance, the step.
         Graphs need use_hip_graph, a CUDA latent, a tensor condition (a dict / None cannot be a static graph input), eps
         parameterisation and no shorten_cond_schedule (the condition changes every step).
         visits: (t, row) per step in visiting order; `row` picks the step's coefficients from the device table `coefs`.
-        epilogue(cur, eps, shift, ts, row, noise) -> the next latent; `shift` is None without alignment.
+        epilogue(cur, eps, shift, ts, noise) -> the next latent; `shift` is None without alignment.
         Step noise: _step_noise, drawn from the device generator at the start of the step with draw="early", where the step
         needs it with draw="late" (the reference's ancestral order: after the denoiser and the guidance), zero with None.
-        hold: a held-region run (_hold_operands; DESIGN.md §7, "Held regions") in any of the four modes: the graphs are the "_held" kinds,
-        whose step kernel blends the known latent in, and `epilogue` gets the hold's noise as a seventh argument.  The start rule is one
-        pd_hold_blend launch.  The hold draw of step k follows the step's own tape entry (hold["tape_own"]) or stands in its place."""
+        hold: a held-region run (_hold_operands; DESIGN.md §7, "Held regions") in any of the four modes: the graphs are the rule's held
+        ones, whose step kernel blends the known latent in.  The start rule is one pd_hold_blend launch.  The hold draw of step k
+        follows the step's own tape entry (hold["tape_own"]) or stands in its place."""
         device = self.betas.device
         B = shape[self.batch_axis]
         img = self._start_latent(x_T, noise_tape, shape, device)
@@ -623,7 +616,8 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             img = torch.empty_like(x_T)
             with L.on_device(x_T):
                 L.hold_blend(x_T, hold["x0"], hold["mask"], x_T, hold["start"].expand(B, 2).contiguous(), img, B, x_T[0].numel())
-            kind = kind + "_held"
+        kind = "ddpm" if rule is None else (rule, hold is not None)
+        hist = None                                    # aligned / eager mode: the x0 history of the whole batch, owned by this call
 
         def randn():
             return torch.randn(shape, device=device)
@@ -693,7 +687,15 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
                         shift = self._guidance(cur, ts, cond, y, alignment_kwargs) if use_alignment else None
                     if noise is None and draw == "late":
                         noise = randn()
-                    img = epilogue(cur, eps, shift, ts, row, noise) if hold is None else epilogue(cur, eps, shift, ts, row, noise, hn)
+                    if rule is None:
+                        img = epilogue(cur, eps, shift, ts, noise)
+                    else:
+                        if rule.hist and hist is None:
+                            hist = torch.empty_like(cur)
+                        img = torch.empty_like(cur)
+                        with L.on_device(cur):
+                            launch_step(rule, cur, eps, noise, hist, shift, None if hold is None else (hold["x0"], hold["mask"], hn),
+                                        coefs[row].expand(B, coefs.shape[1]).contiguous(), img)
             if mask is not None:
                 img = self.q_sample(x0, torch.full((B,), t, device=device, dtype=torch.long)) * mask + (1.0 - mask) * img
             if return_intermediates and (t % log_every_t == 0 or k == 0):
@@ -726,22 +728,22 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
             return self.p_sample(zt=img, zc=cond, t=ts, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
                                  clip_denoised=self.clip_denoised, noise=noise)
 
-        def epilogue(cur, eps, shift, ts, row, noise):
+        def epilogue(cur, eps, shift, ts, noise):
             return self._ddpm_update(cur, eps, noise, shift, ts, 1.0, self.clip_denoised)
-        return self._run_sampler("ddpm", cond, shape, x_T, noise_tape, [(i, None) for i in reversed(range(timesteps))], epilogue,
-                                 draw="late", eager=eager, use_alignment=use_alignment, y=y, alignment_kwargs=alignment_kwargs,
+        return self._run_sampler(None, cond, shape, x_T, noise_tape, [(i, None) for i in reversed(range(timesteps))], draw="late",
+                                 epilogue=epilogue, eager=eager, use_alignment=use_alignment, y=y, alignment_kwargs=alignment_kwargs,
                                  return_intermediates=return_intermediates, log_every_t=log_every_t or self.log_every_t, mask=mask,
                                  x0=x0, callback=callback, img_callback=img_callback)
 
     # ------------------------------------------------------------------------------------------------ held regions
     @staticmethod
     def _check_hold(hold_mask, hold_x0, hold_noise, sampler=None):
-        """What a held-region call refuses before any draw; True when there is a hold."""
+        """What a held-region call refuses before any draw (`sampler`: `sample`'s, when the caller has one); True when there is a hold."""
         if hold_noise not in HOLD_NOISE:
             raise ValueError(f"hold_noise must be one of {HOLD_NOISE}; got {hold_noise!r}")
         if (hold_mask is None) != (hold_x0 is None):
             raise ValueError("hold_mask and hold_x0 go together: got only " + ("hold_x0" if hold_mask is None else "hold_mask"))
-        if hold_mask is not None and sampler == "ddpm":
+        if hold_mask is not None and sampler is not None and sampler not in RULES:
             raise NotImplementedError('hold_mask / hold_x0 are defined for sampler="ddim" | "dpmpp_2m" | "dpmpp_2m_sde"; the ancestral '
                                       "sampler takes the reference's mask / x0")
         return hold_mask is not None
@@ -765,8 +767,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
 
     def _hold_schedule(self, hold, table, guided, steps, visited, tape_own):
         """The schedule's part of a hold: `table` (one row per visited step, in visiting order) widened by gamma = 0 when the run is not
-        guided and by the hold columns of schedule.make_hold_coefficients (`visited`: the grid indices in visiting order, None for
-        DDIM's); the start row; and whether the sampler's own step reads a tape entry (then the hold draw follows it, else it stands
+        guided and by the hold columns of schedule.make_hold_coefficients (`visited`: the grid indices in visiting order); the start row; and whether the sampler's own step reads a tape entry (then the hold draw follows it, else it stands
         in its place)."""
         cols, start = make_hold_coefficients(self._alphas_cumprod_f64.astype(np.float32).astype(np.float64), steps, visited)
         if not guided:
@@ -796,6 +797,38 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         mask[:, first:first + k] = 1.0
         return mask, x0
 
+    def _fast_sample_loop(self, rule, cond, shape, n_steps, eta, discretize, lower_order_final, x_T, noise_tape, return_intermediates,
+                          use_alignment, alignment_kwargs, y, hold_mask, hold_x0, hold_noise):
+        """What ddim_sample_loop, dpmpp_2m_sample_loop and dpmpp_2m_sde_sample_loop share, which is everything but `rule`
+        (step_rules.StepRule): the refusals, all before any draw; the rule's coefficient table, one row per visited step in visiting
+        order, widened by gamma when guided and by (gamma, k_x, k_n) when held; the tape rule; the step driver."""
+        hold = self._hold_operands(hold_mask, hold_x0, hold_noise, shape)
+        if self.shorten_cond_schedule:
+            raise NotImplementedError("shorten_cond_schedule (num_timesteps_cond > 1) is defined for the ancestral loop only")
+        if not (1 <= int(n_steps) <= self.num_timesteps):
+            raise ValueError(f"{rule.steps_kw} must be in [1, {self.num_timesteps}], got {n_steps}")
+        if self.clip_denoised:
+            raise NotImplementedError(f"clip_denoised=True is defined for the ancestral sampler only (the {rule.label} step has no clamp)")
+        if self.parameterization != "eps":
+            raise NotImplementedError(f'parameterization="x0" is defined for the ancestral sampler only (the {rule.label} step reads the '
+                                      "model output as eps)")
+        if use_alignment:
+            assert self.alignment_fn is not None, "Alignment function not set."
+        table, grid, visited = rule.schedule(self, n_steps, eta, discretize, lower_order_final)
+        if use_alignment:      # a grid point that is not visited has an empty J and gamma 0: the visited steps' J still partition {0..grid[-1]}
+            gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), grid)
+            table = np.concatenate([table, gamma[visited, None]], axis=1)
+        own = rule.reads_tape(eta)
+        if hold is not None:
+            table = self._hold_schedule(hold, table, use_alignment, grid, visited, own)
+        coefs = torch.tensor(table, dtype=torch.float32, device=self.betas.device)          # the one rounding to fp32
+        if not own and (hold is None or not hold["fresh"]):
+            # draw 0 is the only draw of the run; the driver gets no tape, so a step-ordered (lazy) tape is read at index 0 and nowhere else
+            x_T, noise_tape = self._start_latent(x_T, noise_tape, shape, self.betas.device), None
+        return self._run_sampler(rule, cond, shape, x_T, noise_tape, [(int(grid[idx]), k) for k, idx in enumerate(visited)], coefs=coefs,
+                                 draw="early" if rule.stochastic(eta) else None, use_alignment=use_alignment, y=y,
+                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates, hold=hold)
+
     @torch.no_grad()
     @_on_own_device
     def ddim_sample_loop(self, cond, shape, ddim_steps=50, eta=0.0, x_T=None, noise_tape=None, return_intermediates=False,
@@ -808,64 +841,8 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         device draw when eta > 0) for step k.
         hold_mask / hold_x0 / hold_noise: a held region ("Held regions"); with "fresh" the tape is
         [x_T, n_0, h_0, ..., n_{K-1}] (no tape: a device draw per h_k, after the step's own), with "fixed" the un-held run's."""
-        B = shape[self.batch_axis]
-        hold = self._hold_operands(hold_mask, hold_x0, hold_noise, shape)
-        if self.shorten_cond_schedule:
-            raise NotImplementedError("shorten_cond_schedule (num_timesteps_cond > 1) is defined for the ancestral loop only")
-        if not (1 <= int(ddim_steps) <= self.num_timesteps):
-            raise ValueError(f"ddim_steps must be in [1, {self.num_timesteps}], got {ddim_steps}")
-        if self.clip_denoised:
-            raise NotImplementedError("clip_denoised=True is defined for the ancestral sampler only (the DDIM step has no clamp)")
-        if self.parameterization != "eps":
-            raise NotImplementedError('parameterization="x0" is defined for the ancestral sampler only (the DDIM step reads the '
-                                      "model output as eps)")
-        if use_alignment:
-            assert self.alignment_fn is not None, "Alignment function not set."
-        steps = np.minimum(make_ddim_timesteps(ddim_discretize, ddim_steps, self.num_timesteps), self.num_timesteps - 1)
-        sig, a, a_prev = make_ddim_sampling_parameters(self._alphas_cumprod_f64.astype(np.float32).astype(np.float64), steps, eta)
-        cols = [a, a_prev, sig]
-        if use_alignment:
-            cols.append(make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), steps))
-        # one row (a_t, a_prev, sigma[, gamma]) per step, rounded from fp64 to fp32 once
-        table, order = np.stack(cols, axis=1), list(reversed(range(len(steps))))
-        rows = order
-        if hold is not None:   # rows (a_t, a_prev, sigma, gamma, k_x, k_n) in visiting order; the step reads a tape entry of its own
-            table, rows = self._hold_schedule(hold, table[order], use_alignment, steps, None, True), list(range(len(order)))
-        coefs = torch.tensor(table, dtype=torch.float32, device=self.betas.device)
-
-        def epilogue(cur, eps, shift, ts, row, noise, hn=None):
-            out = torch.empty_like(cur)
-            coef = coefs[row].expand(B, coefs.shape[1]).contiguous()
-            with L.on_device(cur):
-                if hold is not None:
-                    L.ddim_step_held(cur, eps, noise, shift, hold["x0"], hold["mask"], cur if hn is None else hn, coef, out, B,
-                                     cur[0].numel())
-                elif shift is None:
-                    L.ddim_step(cur, eps, noise if noise is not None else torch.zeros_like(cur), coef, out, B, cur[0].numel())
-                else:
-                    L.ddim_step_guided(cur, eps, noise, shift, coef, out, B, cur[0].numel())
-            return out
-        return self._run_sampler("ddim", cond, shape, x_T, noise_tape, [(int(steps[idx]), row) for idx, row in zip(order, rows)],
-                                 epilogue, coefs=coefs, draw="early" if eta > 0 else None, use_alignment=use_alignment, y=y,
-                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates, hold=hold)
-
-    def _dpmpp_grid(self, steps, discretize, use_alignment):
-        """What the two DPM-Solver++(2M) loops refuse, before any draw, then (alphas_cumprod as fp32 values in fp64, the grid)."""
-        if self.shorten_cond_schedule:
-            raise NotImplementedError("shorten_cond_schedule (num_timesteps_cond > 1) is defined for the ancestral loop only")
-        if not (1 <= int(steps) <= self.num_timesteps):
-            raise ValueError(f"steps must be in [1, {self.num_timesteps}], got {steps}")
-        if self.clip_denoised:
-            raise NotImplementedError("clip_denoised=True is defined for the ancestral sampler only (the DPM-Solver++ step has no clamp)")
-        if self.parameterization != "eps":
-            raise NotImplementedError('parameterization="x0" is defined for the ancestral sampler only (the DPM-Solver++ step reads the '
-                                      "model output as eps)")
-        if use_alignment:
-            assert self.alignment_fn is not None, "Alignment function not set."
-        ac = self._alphas_cumprod_f64.astype(np.float32).astype(np.float64)
-        grid = make_logsnr_timesteps(steps, ac) if discretize == "logsnr" else \
-            np.minimum(make_ddim_timesteps(discretize, steps, self.num_timesteps), self.num_timesteps - 1)
-        return ac, grid
+        return self._fast_sample_loop(DDIM, cond, shape, ddim_steps, eta, ddim_discretize, None, x_T, noise_tape,
+                                      return_intermediates, use_alignment, alignment_kwargs, y, hold_mask, hold_x0, hold_noise)
 
     @torch.no_grad()
     @_on_own_device
@@ -879,39 +856,8 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         use_alignment: z_prev -= gamma_idx * alignment_fn(z_t, steps[idx], zc=cond, y=y, **alignment_kwargs), gamma_idx as guided DDIM.
         hold_mask / hold_x0 / hold_noise: a held region ("Held regions"); "fresh" reads [x_T, h_0, ..., h_{K-2}] (a tape,
         else device draws), "fixed" x_T alone."""
-        B = shape[self.batch_axis]
-        hold = self._hold_operands(hold_mask, hold_x0, hold_noise, shape)
-        ac, grid = self._dpmpp_grid(steps, discretize, use_alignment)
-        table, visited = make_dpmpp_2m_coefficients(ac, grid, lower_order_final)
-        if use_alignment:      # a dropped grid point has an empty J and gamma 0: the visited steps' J still partition {0..grid[-1]}
-            gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), grid)
-            table = np.concatenate([table, gamma[visited, None]], axis=1)
-        if hold is not None:   # rows (a_t, c_x, c_d, w, gamma, k_x, k_n); the step reads no tape entry: the hold draw stands in its place
-            table = self._hold_schedule(hold, table, use_alignment, grid, visited, False)
-        # one row (a_t, c_x, c_d, w[, gamma]) per visited step, in visiting order
-        coefs = torch.tensor(table, dtype=torch.float32, device=self.betas.device)
-        if hold is None or not hold["fresh"]:
-            # the only draw of the run; the driver gets no tape, so a step-ordered (lazy) tape is read at index 0 and nowhere else
-            x_T, noise_tape = self._start_latent(x_T, noise_tape, shape, self.betas.device), None
-        hist = []              # aligned / eager mode: one x0 history for the whole batch, owned by this call
-
-        def epilogue(cur, eps, shift, ts, row, noise, hn=None):
-            if not hist:
-                hist.append(torch.empty_like(cur))
-            out = torch.empty_like(cur)
-            coef = coefs[row].expand(B, coefs.shape[1]).contiguous()
-            with L.on_device(cur):
-                if hold is not None:
-                    L.dpmpp_2m_step_held(cur, eps, hist[0], shift, hold["x0"], hold["mask"], cur if hn is None else hn, coef, out, B,
-                                         cur[0].numel())
-                elif shift is None:
-                    L.dpmpp_2m_step(cur, eps, hist[0], coef, out, B, cur[0].numel())
-                else:
-                    L.dpmpp_2m_step_guided(cur, eps, hist[0], shift, coef, out, B, cur[0].numel())
-            return out
-        return self._run_sampler("dpmpp", cond, shape, x_T, noise_tape, [(int(grid[idx]), k) for k, idx in enumerate(visited)], epilogue,
-                                 coefs=coefs, use_alignment=use_alignment, y=y, alignment_kwargs=alignment_kwargs,
-                                 return_intermediates=return_intermediates, hold=hold)
+        return self._fast_sample_loop(DPMPP_2M, cond, shape, steps, 0.0, discretize, lower_order_final, x_T, noise_tape,
+                                      return_intermediates, use_alignment, alignment_kwargs, y, hold_mask, hold_x0, hold_noise)
 
     @torch.no_grad()
     @_on_own_device
@@ -925,47 +871,15 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         use_alignment: as dpmpp_2m_sample_loop.
         hold_mask / hold_x0 / hold_noise: a held region ("Held regions"); with "fresh" the tape is
         [x_T, n_0, h_0, ..., n_{K-1}] when eta > 0 and dpmpp_2m_sample_loop's [x_T, h_0, ..., h_{K-2}] at eta = 0."""
-        B = shape[self.batch_axis]
-        hold = self._hold_operands(hold_mask, hold_x0, hold_noise, shape)
-        ac, grid = self._dpmpp_grid(steps, discretize, use_alignment)
-        table, visited = make_dpmpp_2m_sde_coefficients(ac, grid, eta, lower_order_final)
-        if use_alignment:
-            gamma = make_ddim_guidance_coefficients(self.posterior_log_variance_clipped.cpu().numpy(), grid)
-            table = np.concatenate([table, gamma[visited, None]], axis=1)
-        stochastic = float(eta) > 0
-        if hold is not None:   # rows (a_t, c_x, c_d, w, c_n, gamma, k_x, k_n); the step reads a tape entry of its own when eta > 0
-            table = self._hold_schedule(hold, table, use_alignment, grid, visited, stochastic)
-        # one row (a_t, c_x, c_d, w, c_n[, gamma]) per visited step, in visiting order
-        coefs = torch.tensor(table, dtype=torch.float32, device=self.betas.device)
-        if not stochastic and (hold is None or not hold["fresh"]):     # as dpmpp_2m_sample_loop: draw 0 is the only draw, and the driver gets no tape
-            x_T, noise_tape = self._start_latent(x_T, noise_tape, shape, self.betas.device), None
-        hist = []              # aligned / eager mode: one x0 history for the whole batch, owned by this call
-
-        def epilogue(cur, eps, shift, ts, row, noise, hn=None):
-            if not hist:
-                hist.append(torch.empty_like(cur))
-            out = torch.empty_like(cur)
-            coef = coefs[row].expand(B, coefs.shape[1]).contiguous()
-            if noise is None:  # eta = 0: every c_n is 0 and the kernel does not read the buffer
-                noise = cur
-            with L.on_device(cur):
-                if hold is not None:
-                    L.dpmpp_2m_sde_step_held(cur, eps, noise, hist[0], shift, hold["x0"], hold["mask"], cur if hn is None else hn, coef,
-                                             out, B, cur[0].numel())
-                elif shift is None:
-                    L.dpmpp_2m_sde_step(cur, eps, noise, hist[0], coef, out, B, cur[0].numel())
-                else:
-                    L.dpmpp_2m_sde_step_guided(cur, eps, noise, hist[0], shift, coef, out, B, cur[0].numel())
-            return out
-        return self._run_sampler("dpmpp_sde", cond, shape, x_T, noise_tape, [(int(grid[idx]), k) for k, idx in enumerate(visited)],
-                                 epilogue, coefs=coefs, draw="early" if stochastic else None, use_alignment=use_alignment, y=y,
-                                 alignment_kwargs=alignment_kwargs, return_intermediates=return_intermediates, hold=hold)
+        return self._fast_sample_loop(DPMPP_2M_SDE, cond, shape, steps, eta, discretize, lower_order_final, x_T, noise_tape,
+                                      return_intermediates, use_alignment, alignment_kwargs, y, hold_mask, hold_x0, hold_noise)
 
     @staticmethod
     def _pop_sampler_kwargs(kwargs):
         """The sampler keywords of `sample` (consumed from its **kwargs), with their defaults."""
         sampler = kwargs.pop("sampler", "ddpm")
-        return dict(sampler=sampler, ddim_steps=kwargs.pop("ddim_steps", None), eta=kwargs.pop("eta", 1.0 if sampler == "dpmpp_2m_sde" else 0.0),
+        eta = RULES[sampler].eta_default if sampler in RULES else 0.0
+        return dict(sampler=sampler, ddim_steps=kwargs.pop("ddim_steps", None), eta=kwargs.pop("eta", eta),
                     steps=kwargs.pop("steps", None), discretize=kwargs.pop("discretize", "quad"),
                     lower_order_final=kwargs.pop("lower_order_final", None))
 
@@ -990,34 +904,20 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         """`sample`'s sampler dispatch on a latent context: the loop's output, undecoded (rollout.rollout_sample calls it per segment).
         mask / x0 keep the reference's meaning (ancestral loop only); hold_mask / hold_x0 / hold_noise are the engine's own held regions
         of the three fast samplers ("Held regions")."""
-        fast = sampler in ("ddim", "dpmpp_2m", "dpmpp_2m_sde")
-        self._check_hold(hold_mask, hold_x0, hold_noise, sampler if fast else "ddpm")
-        hold = dict(hold_mask=hold_mask, hold_x0=hold_x0, hold_noise=hold_noise)
-        if sampler == "ddim":
+        self._check_hold(hold_mask, hold_x0, hold_noise, sampler)
+        rule = RULES.get(sampler)
+        if rule is not None:   # through the public loop method: subclasses (tiled.py) and callers wrap it by name
             if mask is not None:
                 raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
-            return self.ddim_sample_loop(zc, shape, ddim_steps=50 if ddim_steps is None else ddim_steps, eta=eta, x_T=x_T,
-                                         noise_tape=noise_tape, return_intermediates=return_intermediates,
-                                         use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y, **hold)
-        if sampler == "dpmpp_2m":
-            if mask is not None:
-                raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
-            if eta != 0.0:
+            if "eta" not in rule.loop_kw and eta != 0.0:
                 raise NotImplementedError("DPM-Solver++(2M) is a deterministic ODE solver: eta must be 0")
-            if steps is None:
-                steps = 20 if ddim_steps is None else ddim_steps
-            return self.dpmpp_2m_sample_loop(zc, shape, steps=steps, discretize=discretize, lower_order_final=lower_order_final,
-                                             x_T=x_T, noise_tape=noise_tape, return_intermediates=return_intermediates,
-                                             use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y, **hold)
-        if sampler == "dpmpp_2m_sde":
-            if mask is not None:
-                raise NotImplementedError("inpainting (mask / x0) is defined for the ancestral sampler only")
-            if steps is None:
-                steps = 20 if ddim_steps is None else ddim_steps
-            return self.dpmpp_2m_sde_sample_loop(zc, shape, steps=steps, eta=eta, discretize=discretize,
-                                                 lower_order_final=lower_order_final, x_T=x_T, noise_tape=noise_tape,
-                                                 return_intermediates=return_intermediates, use_alignment=use_alignment,
-                                                 alignment_kwargs=alignment_kwargs, y=y, **hold)
+            if rule.steps_kw == "ddim_steps" or steps is None:       # `ddim_steps` is an alias of `steps`
+                steps = rule.default_steps if ddim_steps is None else ddim_steps
+            given = dict(eta=eta, discretize=discretize, lower_order_final=lower_order_final)
+            kw = {rule.steps_kw: steps, **{k: given[k] for k in rule.loop_kw}}
+            return getattr(self, rule.name + "_sample_loop")(zc, shape, x_T=x_T, noise_tape=noise_tape, return_intermediates=return_intermediates,
+                                                            use_alignment=use_alignment, alignment_kwargs=alignment_kwargs, y=y,
+                                                            hold_mask=hold_mask, hold_x0=hold_x0, hold_noise=hold_noise, **kw)
         return self.p_sample_loop(cond=zc, shape=shape, y=y, use_alignment=use_alignment, alignment_kwargs=alignment_kwargs,
                                   return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
                                   mask=mask, x0=x0, noise_tape=noise_tape)
@@ -1033,8 +933,7 @@ class LatentDiffusion(LossEvaluationMixin, _module_base()):
         hold_mask / hold_x0 / hold_noise="fresh"|"fixed": a held region of the three fast samplers (DESIGN.md §7, "Held regions";
         hold_from_frames makes the pair from pixel frames); mask / x0 keep the reference's meaning on the ancestral loop."""
         sampler_kwargs = self._pop_sampler_kwargs(kwargs)
-        fast = sampler_kwargs["sampler"] in ("ddim", "dpmpp_2m", "dpmpp_2m_sde")     # refused before the context is encoded
-        self._check_hold(hold_mask, hold_x0, hold_noise, sampler_kwargs["sampler"] if fast else "ddpm")
+        self._check_hold(hold_mask, hold_x0, hold_noise, sampler_kwargs["sampler"])     # refused before the context is encoded
         noise_tape = kwargs.pop("noise_tape", None)
         if use_alignment:
             assert self.alignment_fn is not None, "Alignment function not set."

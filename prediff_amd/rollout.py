@@ -21,6 +21,7 @@ import torch
 
 from . import _lib as L
 from .ensemble import _LazyTape, member_noise_fn, sample_ensemble
+from .step_rules import FAST_SAMPLERS
 from .tiled import TiledLatentDiffusion
 
 RECONDITION = ("latent", "pixel")
@@ -138,7 +139,7 @@ def rollout_sample(ldm, cond, horizon, stride=None, recondition="latent", batch_
     loop_kw = dict(ldm._pop_sampler_kwargs(kw), timesteps=kw.pop("timesteps", None), verbose=kw.pop("verbose", False))
     if kw:
         raise TypeError(f"rollout_sample got unexpected keyword arguments {sorted(kw)}")
-    if overlap == "hold" and loop_kw["sampler"] not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde"):
+    if overlap == "hold" and loop_kw["sampler"] not in FAST_SAMPLERS:
         raise NotImplementedError('overlap="hold" is defined for sampler="ddim" | "dpmpp_2m" | "dpmpp_2m_sde" (held regions)')
     B = int(batch_size)
     shape = ldm.get_batch_latent_shape(batch_size=B)

@@ -296,7 +296,7 @@ class TiledLatentDiffusion(LatentDiffusion):
     dpmpp_2m_sample_loop = _refusing_alignment("dpmpp_2m_sample_loop")
     dpmpp_2m_sde_sample_loop = _refusing_alignment("dpmpp_2m_sde_sample_loop")
 
-    def _run_sampler(self, kind, cond, shape, *args, **kwargs):
+    def _run_sampler(self, rule, cond, shape, *args, **kwargs):
         """A latent canvas as condition (cond_stage_model=None) becomes the window stack once per run, not once per step, and the
         denoiser's batch mode is chosen from the windows of the whole call (_pins_batch_mode), whatever the lanes make of them."""
         self._refuse_alignment(kwargs.get("use_alignment", False))
@@ -308,6 +308,6 @@ class TiledLatentDiffusion(LatentDiffusion):
             self._graphs, self._graphs_pinned = {}, pin
         self._call_windows = windows
         try:
-            return super()._run_sampler(kind, cond, shape, *args, **kwargs)
+            return super()._run_sampler(rule, cond, shape, *args, **kwargs)
         finally:
             self._call_windows = None
