@@ -635,6 +635,37 @@ int pd_spectrum_update(const float* pred, const float* target, int M, const int6
                        const int64_t* target_strides, const int* cell_order, const int* bin_start, int nb, int window, int keep_seq,
                        double* sums, long long* frames, void* ws, int64_t ws_bytes, pd_stream_t stream);
 
+/* Object-based verification (not in the reference): connected-component labelling of frames, the per-object table, and SAL (Wernli et al.
+ * 2008, Mon. Wea. Rev. 136, 4470).  A frame is one (n, t) image of H x W fp32 pixels, C = 1, 1 <= H, W <= 128 (the label image lives in
+ * LDS; else PD_ERR_ARG, the message names the limit), read in place.  Object pixels: v >= thr and v > 0, with thr = threshold when
+ * use_threshold != 0, else the fp32 product thr_factor * max(frame) of that frame (NaN, hence no object, when the frame holds a NaN).
+ * Objects: the components of that mask under connectivity 4 or 8 that have at least min_pixels pixels, numbered 1, 2, ... in raster order
+ * of their first pixel.
+ * pd_objects_label: sizes / strides: host int64[5] = N, T, H, W, C sizes and element strides.  records: device, N T records of 9
+ * doubles (pd_objects_ws_bytes(0, sizes) bytes): D = sum v / (H W), sum v, sum v row, sum v col (all pixels); sum R_n^2 / P_n, sum R_n,
+ * sum R_n |x - x_n| (objects: mass R, peak P, centroid x_n, x the mass centre of the frame); the object count; flags (1: the frame holds a
+ * non-finite pixel -- it gets labels and a count, and zero object sums).  labels: NULL or device int32 (N, T, H, W), 0 = background.
+ * table: NULL or device fp64 (N, T, max_objects, 6), row k - 1 of object k: mass, peak, area, row centroid, col centroid, first-pixel
+ * index row W + col; objects beyond max_objects are left out of the table only, and rows beyond the count are not written.
+ * Labels, counts, areas and first-pixel indices are exact; the object sums are added as integers (two 40-bit fixed-point limbs relative
+ * to the frame maximum: exact for pixels >= 2^-57 of it) and so is every record: the same frame gives the same bits.
+ * pd_sal_update: pred holds M members of target's shape (1 <= M <= 512; pred_strides: host int64[6] = member, N, T, H, W, C;
+ * target_strides: host int64[5]); the target's frames are labelled once.  Per (member, n, t) pair and step t (t = 0 unless keep_seq), in
+ * fp64 and in a fixed order: a pair with a flagged frame adds 1 to counts[1][t] and nothing else; every other pair adds 1 to counts[0][t],
+ * its object counts to counts[6][t] (pred) and counts[7][t] (target), and, where defined, A = (D_F - D_O) / ((D_F + D_O) / 2) to
+ * sums[1][t] (|A| to sums[6][t], 1 to counts[3][t]; defined when D_F + D_O != 0), S = (V_F - V_O) / ((V_F + V_O) / 2), V = sum R_n^2 / P_n /
+ * sum R_n, to sums[0][t] (|S| to sums[5][t], 1 to counts[2][t]; both frames have an object), L1 = |x_F - x_O| / d to sums[2][t] (1 to
+ * counts[4][t]; both frames have mass; d = sqrt((H - 1)^2 + (W - 1)^2) > 0), L2 = 2 |r_F - r_O| / d, r = sum R_n |x - x_n| / sum R_n, to
+ * sums[3][t] and L1 + L2 to sums[4][t] (1 to counts[5][t]; objects and mass in both).  sums: device fp64 [7][T'], counts: device int64
+ * [8][T'].  ws: device workspace of pd_objects_ws_bytes(M, sizes) bytes, 8-byte aligned (-1: unsupported M / sizes). */
+int64_t pd_objects_ws_bytes(int M, const int64_t* sizes);
+int pd_objects_label(const float* frames, const int64_t* sizes, const int64_t* strides, float threshold, int use_threshold,
+                     float thr_factor, int connectivity, int min_pixels, double* records, int* labels, double* table, int max_objects,
+                     pd_stream_t stream);
+int pd_sal_update(const float* pred, const float* target, int M, const int64_t* sizes, const int64_t* pred_strides,
+                  const int64_t* target_strides, float threshold, int use_threshold, float thr_factor, int connectivity, int min_pixels,
+                  int keep_seq, double* sums, long long* counts, void* ws, int64_t ws_bytes, pd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Fréchet video distance (evaluation/fvd/): the pieces of the I3D feature engine that are not pd_igemm, and the feature moments.
  * ------------------------------------------------------------------------------------------------- */

@@ -198,6 +198,11 @@ _PROTOS = {
     "pd_spectrum_ws_bytes": (C.c_int64, [C.c_int, C.c_void_p]),
     "pd_spectrum_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 3
                            + [C.c_int64, C.c_void_p]),
+    "pd_objects_ws_bytes": (C.c_int64, [C.c_int, C.c_void_p]),
+    "pd_objects_label": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3
+                         + [C.c_int, C.c_void_p]),
+    "pd_sal_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_int, C.c_float] + [C.c_int] * 3
+                      + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "pd_i3d_preprocess": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_maxpool3d_same": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_i3d_head": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
@@ -927,7 +932,29 @@ def spectrum_update(pred, target, M, sizes, pred_strides, target_strides, cell_o
                                     ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "pd_spectrum_update")
 
 
-I3D_RES, I3D_STEM_WO, I3D_STEM_LD = 224, 112, 64          # pd_i3d_preprocess: crop side, operand rows per image row, operand row length
+def objects_ws_bytes(M, sizes):
+    return int(lib().pd_objects_ws_bytes(int(M), _i64(sizes)))
+
+
+def objects_label(frames, sizes, strides, threshold, thr_factor, connectivity, min_pixels, records, labels, table, max_objects):
+    """frames: fp32, read in place through the (N, T, H, W, C) sizes / strides; threshold: None for thr_factor * max(frame); records fp64
+    [N T, 9]; labels: None or int32 (N, T, H, W); table: None or fp64 (N, T, max_objects, 6)."""
+    _check(lib().pd_objects_label(ptr(frames), _i64(sizes), _i64(strides), 0.0 if threshold is None else float(threshold),
+                                  0 if threshold is None else 1, float(thr_factor), int(connectivity), int(min_pixels), ptr(records),
+                                  ptr(labels), ptr(table), int(max_objects), stream_ptr()), "pd_objects_label")
+
+
+def sal_update(pred, target, M, sizes, pred_strides, target_strides, threshold, thr_factor, connectivity, min_pixels, keep_seq, sums,
+               counts, ws):
+    """pred_strides: member stride followed by the (N, T, H, W, C) strides; sums fp64 [7, T'], counts int64 [8, T']; ws: fp64 workspace
+    of objects_ws_bytes(M, sizes) bytes."""
+    _check(lib().pd_sal_update(ptr(pred), ptr(target), int(M), _i64(sizes), _i64(pred_strides), _i64(target_strides),
+                               0.0 if threshold is None else float(threshold), 0 if threshold is None else 1, float(thr_factor),
+                               int(connectivity), int(min_pixels), 1 if keep_seq else 0, ptr(sums), ptr(counts), ptr(ws),
+                               ws.numel() * ws.element_size(), stream_ptr()), "pd_sal_update")
+
+
+I3D_RES, I3D_STEM_WO, I3D_STEM_LD = 224, 112, 64         # pd_i3d_preprocess: crop side, operand rows per image row, operand row length
 
 
 def i3d_preprocess(x, sizes, strides, normalize, auto_t, out, out_lo, out_f32=None, rescale=True, opts=None):

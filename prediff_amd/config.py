@@ -124,13 +124,15 @@ def split_sequence(seq: torch.Tensor, in_len: int, out_len: int):
 @torch.no_grad()
 def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int = 0, rank: int = 0, npy_dir: Optional[str] = None,
                      score=None, aligned_score=None, ensemble_score=None, aligned_ensemble_score=None, frame_score=None,
-                     aligned_frame_score=None, **sample_kwargs):
+                     aligned_frame_score=None, object_score=None, aligned_object_score=None, **sample_kwargs):
     """The sampling part of test_step (train_sevirlr_prediff.py:905-979) for one batch of sequences (B, in_len+out_len, H, W, C).
 
     ensemble_score / aligned_ensemble_score (ensemble_score.SEVIREnsembleScore, layout of the sequences; not in the reference): after the
     loop, updated once with the stacked samples, M = num_samples_per_context members of each of the B contexts.
     frame_score / aligned_frame_score (frame_score.SEVIRFrameScore: the MSE / MAE / SSIM of test_step, :937-965): updated with every
     sample where score / aligned_score are.
+    object_score / aligned_object_score (object_score.SEVIRObjectScore: SAL and the object counts; not in the reference): updated with
+    every sample where frame_score / aligned_frame_score are.
     **sample_kwargs go to ldm.sample unchanged: sampler="ddim", ddim_steps=..., eta=... or sampler="dpmpp_2m", steps=..., discretize=...,
     lower_order_final=..., noise_tape=... or sampler="dpmpp_2m_sde", steps=..., eta=... (both branches run the sampler they name)."""
     import numpy as np
@@ -150,6 +152,8 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
                 aligned_score.update(pred.float(), tgt)
             if aligned_frame_score is not None:
                 aligned_frame_score.update(pred.float(), tgt)
+            if aligned_object_score is not None:
+                aligned_object_score.update(pred.float(), tgt)
             out["aligned_pred"].append(pred)
         if ev.get("eval_unaligned", True):
             pred = ldm.sample(cond={"y": ctx}, batch_size=B, **sample_kwargs).contiguous()
@@ -159,6 +163,8 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
                 score.update(pred.float(), tgt)
             if frame_score is not None:
                 frame_score.update(pred.float(), tgt)
+            if object_score is not None:
+                object_score.update(pred.float(), tgt)
             out["pred"].append(pred)
     if ensemble_score is not None and out["pred"]:
         ensemble_score.update(torch.stack(out["pred"]).float(), tgt)

@@ -1,4 +1,5 @@
-"""What the four SEVIR score classes share (``SEVIRSkillScore``, ``SEVIREnsembleScore``, ``SEVIRFrameScore``, ``SEVIRSpectralScore``):
+"""What the five SEVIR score classes share (``SEVIRSkillScore``, ``SEVIREnsembleScore``, ``SEVIRFrameScore``, ``SEVIRSpectralScore``,
+``SEVIRObjectScore``):
 the N, T, H, W, C view of a tensor in a layout, the constructor checks, the life cycle of the accumulated state and its ``sync``, the
 member-stack checks of ``update`` and the workspace.  A subclass declares its metrics, its state tensors and what its layout must
 name; ``update`` and ``compute`` are its own.
