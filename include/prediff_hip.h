@@ -666,6 +666,30 @@ int pd_sal_update(const float* pred, const float* target, int M, const int64_t* 
                   const int64_t* target_strides, float threshold, int use_threshold, float thr_factor, int connectivity, int min_pixels,
                   int keep_seq, double* sums, long long* counts, void* ws, int64_t ws_bytes, pd_stream_t stream);
 
+/* Probability matching (not in the reference; DESIGN.md §7 "Probability matching"; the definitions are the module docstring of
+ * prediff_amd/probability_matching.py).  A frame is n = H W contiguous fp32 pixels, 1 <= H, W and n <= 16384 (it is sorted in LDS).  ORDER:
+ * ascending by the exact fp32 value (compared as integer keys: denormals are never flushed; -0.0 ties with +0.0), ties by ascending pixel
+ * index.  Every result is a selection of input values: exact, no atomics, the same inputs give the same bits.  No synchronisation and no
+ * host reads: every call can be captured.  Outputs alias no input and not the workspace.
+ * pd_pm_ws_bytes: the workspace of an op (host-only; -1: unsupported): op 0 pd_rank_frames (needs none: 0), op 1 pd_cdf_match with
+ *   `frames` REFERENCE frames: their sorted keys and flags, align8(4 frames n) + align8(4 frames); op 2 pd_pmm with M members of `frames`
+ *   (b, t) frames: two buffers of the pooled keys, 2 align8(4 frames M n).  frames (M) n <= 2^31.
+ * pd_rank_frames: x (frames, n) -> order int32 (frames, n), sorted fp32 (frames, n), sorted[r] = x[order[r]] (the original bits).  A frame
+ *   with a non-finite pixel gets order -1 and sorted NaN throughout.
+ * pd_cdf_match: x (lead, B, T, n), ref (B, ref_T, n) with ref_T = T or 1 (one reference frame for every t) -> out shaped like x.  Per
+ *   frame, s = the sorted reference frame (-0.0 read as +0.0; sorted once per reference frame); with use_threshold, n_x = #{x > threshold}
+ *   and s[r] <- min(s[r], threshold) for r < n - n_x; out[order_x[r]] = s[r].  A non-finite pixel in the frame of x or of ref makes the
+ *   output frame NaN.  ws: pd_pm_ws_bytes(1, 1, B ref_T, H, W) bytes, 8-byte aligned.
+ * pd_pmm: ens (M, frames, n), 1 <= M <= 512 -> out (frames, n).  Per frame: mean = float(sum_m double(ens[m]) / M) (fp64 sum in member
+ *   order, fp64 division, one rounding); P = the M n member values in ascending order (-0.0 read as +0.0);
+ *   out[order_mean[r]] = P[r M + M / 2].  A non-finite pixel in any member's frame makes the output frame NaN.
+ *   ws: pd_pm_ws_bytes(2, M, frames, H, W) bytes, 8-byte aligned. */
+int64_t pd_pm_ws_bytes(int op, int M, int64_t frames, int H, int W);
+int pd_rank_frames(const float* x, int64_t frames, int H, int W, float* sorted, int* order, pd_stream_t stream);
+int pd_cdf_match(const float* x, const float* ref, int64_t lead, int64_t B, int T, int ref_T, int H, int W, float threshold,
+                 int use_threshold, float* out, void* ws, int64_t ws_bytes, pd_stream_t stream);
+int pd_pmm(const float* ens, int M, int64_t frames, int H, int W, float* out, void* ws, int64_t ws_bytes, pd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Fréchet video distance (evaluation/fvd/): the pieces of the I3D feature engine that are not pd_igemm, and the feature moments.
  * ------------------------------------------------------------------------------------------------- */

@@ -21,3 +21,4 @@ from .object_score import SEVIRObjectScore, label_objects  # noqa: E402,F401
 from .extrapolation import LagrangianPersistence  # noqa: E402,F401
 from .steps import StochasticExtrapolation, steps_bands  # noqa: E402,F401
 from .anvil import AutoregressiveExtrapolation  # noqa: E402,F401
+from .probability_matching import match_cdf, probability_matched_mean, rank_frames  # noqa: E402,F401

@@ -203,6 +203,11 @@ _PROTOS = {
                          + [C.c_int, C.c_void_p]),
     "pd_sal_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_int, C.c_float] + [C.c_int] * 3
                       + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "pd_pm_ws_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "pd_rank_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "pd_cdf_match": (C.c_int, [C.c_void_p] * 2 + [C.c_int64] * 2 + [C.c_int] * 4 + [C.c_float, C.c_int] + [C.c_void_p] * 2
+                     + [C.c_int64, C.c_void_p]),
+    "pd_pmm": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int64, C.c_void_p]),
     "pd_i3d_preprocess": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_maxpool3d_same": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_i3d_head": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
@@ -952,6 +957,48 @@ def sal_update(pred, target, M, sizes, pred_strides, target_strides, threshold, 
                                0.0 if threshold is None else float(threshold), 0 if threshold is None else 1, float(thr_factor),
                                int(connectivity), int(min_pixels), 1 if keep_seq else 0, ptr(sums), ptr(counts), ptr(ws),
                                ws.numel() * ws.element_size(), stream_ptr()), "pd_sal_update")
+
+
+PM_RANK, PM_CDF, PM_PMM = 0, 1, 2                        # the ops of pd_pm_ws_bytes
+
+
+def pm_ws_bytes(op, M, frames, H, W):
+    """pd_pm_ws_bytes: the workspace of op PM_RANK (0: none) / PM_CDF (`frames` reference frames) / PM_PMM (M members of `frames`
+    frames); -1 for an unsupported shape (host-only)."""
+    return int(lib().pd_pm_ws_bytes(int(op), int(M), int(frames), int(H), int(W)))
+
+
+def _pm_operands(fn, device, operands):
+    for name, x, dtype, need in operands:
+        if x.dtype != dtype or not x.is_contiguous() or not x.is_cuda or x.device != device or x.numel() != need:
+            raise PrediffHipError(f"{fn}: {name} must be a contiguous {dtype} tensor of {need} elements on {device}, got {tuple(x.shape)} "
+                                  f"{x.dtype} on {x.device}")
+
+
+def rank_frames(x, frames, H, W, sorted_out, order):
+    """pd_rank_frames: x (frames, H W) fp32 -> sorted_out fp32, order int32, both (frames, H W)."""
+    n = frames * H * W
+    _pm_operands("rank_frames", x.device, (("x", x, torch.float32, n), ("sorted", sorted_out, torch.float32, n), ("order", order, torch.int32, n)))
+    _check(lib().pd_rank_frames(ptr(x), int(frames), int(H), int(W), ptr(sorted_out), ptr(order), stream_ptr()), "pd_rank_frames")
+
+
+def cdf_match(x, ref, lead, B, T, ref_T, H, W, threshold, out, ws):
+    """pd_cdf_match: x (lead, B, T, H W), ref (B, ref_T, H W), ref_T = T or 1 -> out like x; threshold: None or a finite number; ws: a
+    device tensor of at least pm_ws_bytes(PM_CDF, 1, B * ref_T, H, W) bytes."""
+    _dev(ws)
+    n = lead * B * T * H * W
+    _pm_operands("cdf_match", x.device, (("x", x, torch.float32, n), ("ref", ref, torch.float32, B * ref_T * H * W), ("out", out, torch.float32, n)))
+    _check(lib().pd_cdf_match(ptr(x), ptr(ref), int(lead), int(B), int(T), int(ref_T), int(H), int(W),
+                              0.0 if threshold is None else float(threshold), 0 if threshold is None else 1, ptr(out), ptr(ws),
+                              ws.numel() * ws.element_size(), stream_ptr()), "pd_cdf_match")
+
+
+def pmm(ens, M, frames, H, W, out, ws):
+    """pd_pmm: ens (M, frames, H W) -> out (frames, H W); ws: a device tensor of at least pm_ws_bytes(PM_PMM, M, frames, H, W) bytes."""
+    _dev(ws)
+    _pm_operands("pmm", ens.device, (("ens", ens, torch.float32, M * frames * H * W), ("out", out, torch.float32, frames * H * W)))
+    _check(lib().pd_pmm(ptr(ens), int(M), int(frames), int(H), int(W), ptr(out), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
+           "pd_pmm")
 
 
 I3D_RES, I3D_STEM_WO, I3D_STEM_LD = 224, 112, 64         # pd_i3d_preprocess: crop side, operand rows per image row, operand row length
