@@ -326,144 +326,32 @@ extern "C" int pd_ddpm_step(const float* zt, const float* eps, const float* nois
   return PD_OK;
 }
 
-// ---- DDIM step (parity-unpinned; see header) ----
-// GUIDED: coefficient rows (a_t, a_prev, sigma, gamma) and the knowledge-alignment shift, subtracted as the very last operation
-// (out - gamma * shift), so a zero shift gives the un-guided result bit for bit.  The shift pointer is a trailing parameter pack
-// (one pointer when GUIDED, none otherwise): the un-guided instantiation has exactly the kernel arguments, and so the kernel-argument
-// offsets and the instruction stream, of the single-mode kernel it replaces.
-template <typename P> __device__ __forceinline__ P first_of(P p) { return p; }
-template <bool GUIDED, typename... Shift>
-__global__ void __launch_bounds__(256) ddim_step_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
-                                                        const float* __restrict__ noise, const float* __restrict__ coef,
-                                                        float* __restrict__ out, int64_t per, const Shift* __restrict__... shift) {
-  static_assert(sizeof...(Shift) == (GUIDED ? 1 : 0), "the guided step takes one shift pointer, the un-guided none");
-  constexpr int NC = GUIDED ? 4 : 3;
-  const int b = blockIdx.y;
-  const float a_t = coef[b * NC], a_prev = coef[b * NC + 1], sigma = coef[b * NC + 2];
-  const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t), sp = sqrtf(a_prev);
-  const float dir = sqrtf(fmaxf(0.f, 1.f - a_prev - sigma * sigma));
-  const int64_t base = (int64_t)b * per;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
-    const float e = eps[base + i];
-    const float z0 = (zt[base + i] - s1 * e) * r;
-    float v = sp * z0 + dir * e + (noise ? sigma * noise[base + i] : 0.f);
-    if constexpr (GUIDED) v = v - coef[b * NC + 3] * first_of(shift...)[base + i];
-    out[base + i] = v;
-  }
-}
-extern "C" int pd_ddim_step(const float* zt, const float* eps, const float* noise, const float* coef, float* out, int B,
-                            int64_t per_sample, pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && coef && out && B > 0, "pd_ddim_step: bad args");
-  hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, coef, out,
-                     per_sample);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
-}
-extern "C" int pd_ddim_step_guided(const float* zt, const float* eps, const float* noise, const float* shift, const float* coef4, float* out,
-                                   int B, int64_t per_sample, pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && shift && coef4 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_ddim_step_guided: bad args");
-  hipLaunchKernelGGL((ddim_step_kernel<true, float>), dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, coef4, out,
-                     per_sample, shift);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
-}
+// ---- the fast samplers' step: DDIM, DPM-Solver++(2M) and its SDE form, each plain, guided and held ----
+// One body, nine instantiations: what the forms share they share as source, so a held step under mask 0, a guided step with a zero
+// shift and the SDE step at c_n = 0 give the plainer form's bits by construction.  Contraction is off and every fused operation is a
+// spelled fmaf: the compiler chooses none of the roundings.  (DDIM is parity-unpinned; see the header.  2M and 2M-SDE have no reference
+// implementation: schedule.make_dpmpp_2m_coefficients, schedule.make_dpmpp_2m_sde_coefficients.)
+//
+// SOLVER  row (one per sample)            v, the step's own result
+//   0     a_t, a_prev, sigma              sqrt(a_prev) z0 + dir eps + sigma noise    a null `noise` adds 0.f (eta = 0)
+//   1     a_t, c_x, c_d, w                c_x z + c_d D,  D = z0 + w (z0 - hist)
+//   2     a_t, c_x, c_d, w, c_n           ... + c_n noise
+// then gamma where GUIDED, or (gamma, k_x, k_n) where HELD.  z0 = (z - sqrt(1 - a_t) eps) / sqrt(a_t).
+//
+// `hist` holds the previous step's x0 and is overwritten in place with this step's (every element is read, then written, by the one
+// thread that owns it).  w, c_n and k_n are per sample, so the tests on them are wave-uniform.  With w == 0 (the first step, the
+// lower-order final step) hist is NOT read: a captured graph's history buffer holds stale or uninitialised data there, and 0 * NaN must
+// not reach the output.  With c_n == 0 (eta = 0) the step noise is NOT read, with k_n == 0 (the last step) the hold noise is not.
+// Guidance is the step's last operation, v - gamma shift: compile time in the un-held forms, the test of a pointer in the held ones, whose
+// rows always carry gamma.  The hold follows it: held = k_x x0 + k_n hnoise  and  out = m == 0 ? v : m == 1 ? held : m held + (1 - m) v.
+// The two end points of the mask are selects: a NaN in x0 / hnoise under m == 0, or in v under m == 1, stays where it is.
+struct step_operands {         // operands a form does not have are null
+  const float *__restrict__ zt, *__restrict__ eps, *__restrict__ noise, *__restrict__ shift, *__restrict__ x0, *__restrict__ mask,
+      *__restrict__ hnoise, *__restrict__ coef;
+  float *__restrict__ hist, *__restrict__ out;
+  int64_t per;
+};
 
-// ---- DPM-Solver++(2M) step, data prediction (no reference implementation; DESIGN.md §7, schedule.make_dpmpp_2m_coefficients) ----
-// Coefficient rows (a_t, c_x, c_d, w[, gamma]) per sample.  `hist` holds the previous step's x0 and is overwritten in place with this
-// step's (every element is read, then written, by the one thread that owns it).  w is per sample, so the `w != 0` test is wave-uniform;
-// with w == 0 (the first step, the lower-order final step) hist is NOT read: a captured graph's history buffer holds stale or
-// uninitialised data there, and 0 * NaN must not reach the output.  GUIDED: as ddim_step_kernel, `- gamma * shift` last.
-template <bool GUIDED, typename... Shift>
-__global__ void __launch_bounds__(256) dpmpp_2m_step_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
-                                                            float* __restrict__ hist, const float* __restrict__ coef,
-                                                            float* __restrict__ out, int64_t per, const Shift* __restrict__... shift) {
-  static_assert(sizeof...(Shift) == (GUIDED ? 1 : 0), "the guided step takes one shift pointer, the un-guided none");
-  constexpr int NC = GUIDED ? 5 : 4;
-  const int b = blockIdx.y;
-  const float a_t = coef[b * NC], c_x = coef[b * NC + 1], c_d = coef[b * NC + 2], w = coef[b * NC + 3];
-  const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t);
-  const bool second_order = w != 0.f;
-  const int64_t base = (int64_t)b * per;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
-    const float z = zt[base + i];
-    const float z0 = fmaf(-s1, eps[base + i], z) * r;      // explicit FMAs: both instantiations round alike, whatever the contraction pass picks
-    float d = z0;
-    if (second_order) d = fmaf(w, z0 - hist[base + i], z0);
-    float v = fmaf(c_d, d, c_x * z);
-    if constexpr (GUIDED) v = v - coef[b * NC + 4] * first_of(shift...)[base + i];
-    out[base + i] = v;
-    hist[base + i] = z0;
-  }
-}
-extern "C" int pd_dpmpp_2m_step(const float* zt, const float* eps, float* hist, const float* coef4, float* out, int B, int64_t per_sample,
-                                pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && hist && coef4 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_step: bad args");
-  hipLaunchKernelGGL(dpmpp_2m_step_kernel<false>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, hist, coef4, out,
-                     per_sample);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
-}
-extern "C" int pd_dpmpp_2m_step_guided(const float* zt, const float* eps, float* hist, const float* shift, const float* coef5, float* out,
-                                       int B, int64_t per_sample, pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && hist && shift && coef5 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_step_guided: bad args");
-  hipLaunchKernelGGL((dpmpp_2m_step_kernel<true, float>), dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, hist, coef5,
-                     out, per_sample, shift);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
-}
-
-// ---- SDE-DPM-Solver++(2M) step (schedule.make_dpmpp_2m_sde_coefficients) ----
-// dpmpp_2m_step_kernel with a noise term: rows (a_t, c_x, c_d, w, c_n[, gamma]) per sample, out = c_x z + c_d D + c_n n.  c_n is per
-// sample like w, so the `c_n != 0` test is wave-uniform; with c_n == 0 (eta = 0) the noise buffer is NOT read and the operations
-// are dpmpp_2m_step_kernel's in its order, so the result is pd_dpmpp_2m_step's bit for bit whatever the buffer holds.
-template <bool GUIDED, typename... Shift>
-__global__ void __launch_bounds__(256) dpmpp_2m_sde_step_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
-                                                                const float* __restrict__ noise, float* __restrict__ hist,
-                                                                const float* __restrict__ coef, float* __restrict__ out, int64_t per,
-                                                                const Shift* __restrict__... shift) {
-  static_assert(sizeof...(Shift) == (GUIDED ? 1 : 0), "the guided step takes one shift pointer, the un-guided none");
-  constexpr int NC = GUIDED ? 6 : 5;
-  const int b = blockIdx.y;
-  const float a_t = coef[b * NC], c_x = coef[b * NC + 1], c_d = coef[b * NC + 2], w = coef[b * NC + 3], c_n = coef[b * NC + 4];
-  const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t);
-  const bool second_order = w != 0.f, stochastic = c_n != 0.f;
-  const int64_t base = (int64_t)b * per;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
-    const float z = zt[base + i];
-    const float z0 = fmaf(-s1, eps[base + i], z) * r;
-    float d = z0;
-    if (second_order) d = fmaf(w, z0 - hist[base + i], z0);
-    float v = fmaf(c_d, d, c_x * z);
-    if (stochastic) v = fmaf(c_n, noise[base + i], v);
-    if constexpr (GUIDED) v = v - coef[b * NC + 5] * first_of(shift...)[base + i];
-    out[base + i] = v;
-    hist[base + i] = z0;
-  }
-}
-extern "C" int pd_dpmpp_2m_sde_step(const float* zt, const float* eps, const float* noise, float* hist, const float* coef5, float* out, int B,
-                                    int64_t per_sample, pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && noise && hist && coef5 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_sde_step: bad args");
-  hipLaunchKernelGGL(dpmpp_2m_sde_step_kernel<false>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, hist,
-                     coef5, out, per_sample);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
-}
-extern "C" int pd_dpmpp_2m_sde_step_guided(const float* zt, const float* eps, const float* noise, float* hist, const float* shift,
-                                           const float* coef6, float* out, int B, int64_t per_sample, pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && noise && hist && shift && coef6 && out && B > 0 && B <= 65535 && per_sample > 0,
-               "pd_dpmpp_2m_sde_step_guided: bad args");
-  hipLaunchKernelGGL((dpmpp_2m_sde_step_kernel<true, float>), dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise,
-                     hist, coef6, out, per_sample, shift);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
-}
-
-// ---- held-region (inpainting) forms of the three step kernels ("Held regions") ----
-// The step's own result v, then  held = k_x x0 + k_n hnoise  and  out = m == 0 ? v : m == 1 ? held : m held + (1 - m) v  in the same
-// launch.  Rows: the un-held row, gamma (read only with a shift pointer), then (k_x, k_n).  v is spelled with the operations the
-// un-held kernels compile to (the products they fuse are explicit FMAs here, and contraction is off, so nothing else is fused): where
-// m == 0 the output is theirs bit for bit.  The two end points of the mask are selects: a NaN in x0 / hnoise under m == 0, or in v under
-// m == 1, stays where it is.  k_n is per sample like w and c_n: with k_n == 0 (the last step) hnoise is NOT read.
 __device__ __forceinline__ float hold_select(float v, float m, float x0, const float* hnoise, int64_t j, float k_x, float k_n) {
 #pragma clang fp contract(off)
   float held = k_x * x0;
@@ -472,92 +360,100 @@ __device__ __forceinline__ float hold_select(float v, float m, float x0, const f
   return m == 0.f ? v : m == 1.f ? held : mix;
 }
 
-__global__ void __launch_bounds__(256) ddim_step_held_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
-                                                             const float* __restrict__ noise, const float* __restrict__ shift,
-                                                             const float* __restrict__ x0, const float* __restrict__ mask,
-                                                             const float* __restrict__ hnoise, const float* __restrict__ coef,
-                                                             float* __restrict__ out, int64_t per) {
+template <int SOLVER, bool GUIDED, bool HELD>
+__global__ void __launch_bounds__(256) step_kernel(const step_operands p) {
 #pragma clang fp contract(off)
-  constexpr int NC = 6;                          // a_t, a_prev, sigma, gamma, k_x, k_n
-  const int b = blockIdx.y;
-  const float a_t = coef[b * NC], a_prev = coef[b * NC + 1], sigma = coef[b * NC + 2], gamma = coef[b * NC + 3];
-  const float k_x = coef[b * NC + 4], k_n = coef[b * NC + 5];
-  const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t), sp = sqrtf(a_prev);
-  const float dir = sqrtf(fmaxf(0.f, fmaf(-sigma, sigma, 1.f - a_prev)));
-  const int64_t base = (int64_t)b * per;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
-    const float e = eps[base + i];
-    const float z0 = fmaf(-s1, e, zt[base + i]) * r;
-    float v = fmaf(dir, e, sp * z0) + (noise ? sigma * noise[base + i] : 0.f);
-    if (shift) v = fmaf(-gamma, shift[base + i], v);
-    out[base + i] = hold_select(v, mask[base + i], x0[base + i], hnoise, base + i, k_x, k_n);
-  }
-}
-
-// SDE = false: rows (a_t, c_x, c_d, w, gamma, k_x, k_n) and no noise pointer; SDE = true: rows (a_t, c_x, c_d, w, c_n, gamma, k_x, k_n)
-template <bool SDE>
-__global__ void __launch_bounds__(256) dpmpp_2m_step_held_kernel(const float* __restrict__ zt, const float* __restrict__ eps,
-                                                                 const float* __restrict__ noise, float* __restrict__ hist,
-                                                                 const float* __restrict__ shift, const float* __restrict__ x0,
-                                                                 const float* __restrict__ mask, const float* __restrict__ hnoise,
-                                                                 const float* __restrict__ coef, float* __restrict__ out, int64_t per) {
-#pragma clang fp contract(off)
-  constexpr int NC = SDE ? 8 : 7, G = SDE ? 5 : 4;
-  const int b = blockIdx.y;
-  const float a_t = coef[b * NC], c_x = coef[b * NC + 1], c_d = coef[b * NC + 2], w = coef[b * NC + 3];
-  const float c_n = SDE ? coef[b * NC + 4] : 0.f;
-  const float gamma = coef[b * NC + G], k_x = coef[b * NC + G + 1], k_n = coef[b * NC + G + 2];
+  static_assert(SOLVER >= 0 && SOLVER <= 2 && !(GUIDED && HELD), "three solvers; a held form takes its guidance at run time");
+  constexpr int W = SOLVER + 3, NC = W + (HELD ? 3 : GUIDED ? 1 : 0);
+  const unsigned b = blockIdx.y;
+  const float* row = p.coef + b * NC;
+  const float a_t = row[0];
+  const float a_prev = row[1], sigma = row[2];                  // columns 1 and 2 by DDIM's names ...
+  const float c_x = row[1], c_d = row[2];                       // ... and by 2M's; each solver uses its own
+  const float w = SOLVER >= 1 ? row[3] : 0.f, c_n = SOLVER == 2 ? row[4] : 0.f;
+  const float gamma = GUIDED || HELD ? row[W] : 0.f, k_x = HELD ? row[W + 1] : 0.f, k_n = HELD ? row[W + 2] : 0.f;
+  const float dir = sqrtf(fmaxf(0.f, fmaf(-sigma, sigma, 1.f - a_prev))), sp = sqrtf(a_prev);      // DDIM only
   const float s1 = sqrtf(1.f - a_t), r = 1.f / sqrtf(a_t);
-  const bool second_order = w != 0.f, stochastic = c_n != 0.f;
-  const int64_t base = (int64_t)b * per;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
-    const float z = zt[base + i];
-    const float z0 = fmaf(-s1, eps[base + i], z) * r;
-    float d = z0;
-    if (second_order) d = fmaf(w, z0 - hist[base + i], z0);
-    float v = fmaf(c_d, d, c_x * z);
-    if constexpr (SDE) {
-      if (stochastic) v = fmaf(c_n, noise[base + i], v);
+  const int64_t base = (int64_t)b * p.per;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.per; i += (int64_t)gridDim.x * 256) {
+    const int64_t j = base + i;
+    const float z = p.zt[j], e = p.eps[j];
+    const float z0 = fmaf(-s1, e, z) * r;
+    float v;
+    if constexpr (SOLVER == 0) {
+      v = fmaf(dir, e, sp * z0) + (p.noise ? sigma * p.noise[j] : 0.f);
+    } else {
+      float d = z0;
+      if (w != 0.f) d = fmaf(w, z0 - p.hist[j], z0);
+      v = fmaf(c_d, d, c_x * z);
+      if (SOLVER == 2 && c_n != 0.f) v = fmaf(c_n, p.noise[j], v);
     }
-    if (shift) v = fmaf(-gamma, shift[base + i], v);
-    out[base + i] = hold_select(v, mask[base + i], x0[base + i], hnoise, base + i, k_x, k_n);
-    hist[base + i] = z0;
+    if (HELD ? p.shift != nullptr : GUIDED) v = fmaf(-gamma, p.shift[j], v);
+    if constexpr (HELD) v = hold_select(v, p.mask[j], p.x0[j], p.hnoise, j, k_x, k_n);
+    p.out[j] = v;
+    if constexpr (SOLVER != 0) p.hist[j] = z0;
   }
 }
 
-#define PD_CHECK_HOLD(fn) \
-  PD_CHECK_ARG(hold_x0 && hold_mask && hold_noise, fn ": hold_x0 / hold_mask / hold_noise must not be null (hold_noise is not read where k_n == 0)")
+// The launcher behind the nine entry points.  `noise` may be null for DDIM only, `shift` for a held form only.
+template <int SOLVER, bool GUIDED, bool HELD>
+static int launch_step(const char* fn, const step_operands& p, int B, pd_stream_t stream) {
+  PD_CHECK_ARG(p.zt && p.eps && p.coef && p.out && (SOLVER != 2 || p.noise) && (SOLVER == 0 || p.hist) && (!GUIDED || p.shift) && B > 0 &&
+                   B <= 65535 && p.per > 0,
+               "%s: bad args", fn);
+  PD_CHECK_ARG(!HELD || (p.x0 && p.mask && p.hnoise),
+               "%s: hold_x0 / hold_mask / hold_noise must not be null (hold_noise is not read where k_n == 0)", fn);
+  hipLaunchKernelGGL((step_kernel<SOLVER, GUIDED, HELD>), dim3(grid_for(p.per), B), dim3(256), 0, (hipStream_t)stream, p);
+  PD_CHECK_LAUNCH();
+  return PD_OK;
+}
 
+// step_operands in its order: zt, eps, noise, shift, x0, mask, hnoise, coef, hist, out, per
+#define NIL nullptr
+extern "C" int pd_ddim_step(const float* zt, const float* eps, const float* noise, const float* coef, float* out, int B,
+                            int64_t per_sample, pd_stream_t stream) {
+  return launch_step<0, false, false>("pd_ddim_step", {zt, eps, noise, NIL, NIL, NIL, NIL, coef, NIL, out, per_sample}, B, stream);
+}
+extern "C" int pd_ddim_step_guided(const float* zt, const float* eps, const float* noise, const float* shift, const float* coef4, float* out,
+                                   int B, int64_t per_sample, pd_stream_t stream) {
+  return launch_step<0, true, false>("pd_ddim_step_guided", {zt, eps, noise, shift, NIL, NIL, NIL, coef4, NIL, out, per_sample}, B, stream);
+}
 extern "C" int pd_ddim_step_held(const float* zt, const float* eps, const float* noise, const float* shift, const float* hold_x0,
                                  const float* hold_mask, const float* hold_noise, const float* coef6, float* out, int B, int64_t per_sample,
                                  pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && coef6 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_ddim_step_held: bad args");
-  PD_CHECK_HOLD("pd_ddim_step_held");
-  hipLaunchKernelGGL(ddim_step_held_kernel, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, shift, hold_x0,
-                     hold_mask, hold_noise, coef6, out, per_sample);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
+  return launch_step<0, false, true>("pd_ddim_step_held", {zt, eps, noise, shift, hold_x0, hold_mask, hold_noise, coef6, NIL, out, per_sample},
+                                     B, stream);
+}
+extern "C" int pd_dpmpp_2m_step(const float* zt, const float* eps, float* hist, const float* coef4, float* out, int B, int64_t per_sample,
+                                pd_stream_t stream) {
+  return launch_step<1, false, false>("pd_dpmpp_2m_step", {zt, eps, NIL, NIL, NIL, NIL, NIL, coef4, hist, out, per_sample}, B, stream);
+}
+extern "C" int pd_dpmpp_2m_step_guided(const float* zt, const float* eps, float* hist, const float* shift, const float* coef5, float* out,
+                                       int B, int64_t per_sample, pd_stream_t stream) {
+  return launch_step<1, true, false>("pd_dpmpp_2m_step_guided", {zt, eps, NIL, shift, NIL, NIL, NIL, coef5, hist, out, per_sample}, B, stream);
 }
 extern "C" int pd_dpmpp_2m_step_held(const float* zt, const float* eps, float* hist, const float* shift, const float* hold_x0,
                                      const float* hold_mask, const float* hold_noise, const float* coef7, float* out, int B,
                                      int64_t per_sample, pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && hist && coef7 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_step_held: bad args");
-  PD_CHECK_HOLD("pd_dpmpp_2m_step_held");
-  hipLaunchKernelGGL(dpmpp_2m_step_held_kernel<false>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps,
-                     (const float*)nullptr, hist, shift, hold_x0, hold_mask, hold_noise, coef7, out, per_sample);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
+  return launch_step<1, false, true>("pd_dpmpp_2m_step_held", {zt, eps, NIL, shift, hold_x0, hold_mask, hold_noise, coef7, hist, out, per_sample},
+                                     B, stream);
+}
+extern "C" int pd_dpmpp_2m_sde_step(const float* zt, const float* eps, const float* noise, float* hist, const float* coef5, float* out, int B,
+                                    int64_t per_sample, pd_stream_t stream) {
+  return launch_step<2, false, false>("pd_dpmpp_2m_sde_step", {zt, eps, noise, NIL, NIL, NIL, NIL, coef5, hist, out, per_sample}, B, stream);
+}
+extern "C" int pd_dpmpp_2m_sde_step_guided(const float* zt, const float* eps, const float* noise, float* hist, const float* shift,
+                                           const float* coef6, float* out, int B, int64_t per_sample, pd_stream_t stream) {
+  return launch_step<2, true, false>("pd_dpmpp_2m_sde_step_guided", {zt, eps, noise, shift, NIL, NIL, NIL, coef6, hist, out, per_sample}, B,
+                                     stream);
 }
 extern "C" int pd_dpmpp_2m_sde_step_held(const float* zt, const float* eps, const float* noise, float* hist, const float* shift,
                                          const float* hold_x0, const float* hold_mask, const float* hold_noise, const float* coef8, float* out,
                                          int B, int64_t per_sample, pd_stream_t stream) {
-  PD_CHECK_ARG(zt && eps && noise && hist && coef8 && out && B > 0 && B <= 65535 && per_sample > 0, "pd_dpmpp_2m_sde_step_held: bad args");
-  PD_CHECK_HOLD("pd_dpmpp_2m_sde_step_held");
-  hipLaunchKernelGGL(dpmpp_2m_step_held_kernel<true>, dim3(grid_for(per_sample), B), dim3(256), 0, (hipStream_t)stream, zt, eps, noise, hist,
-                     shift, hold_x0, hold_mask, hold_noise, coef8, out, per_sample);
-  PD_CHECK_LAUNCH();
-  return PD_OK;
+  return launch_step<2, false, true>("pd_dpmpp_2m_sde_step_held",
+                                     {zt, eps, noise, shift, hold_x0, hold_mask, hold_noise, coef8, hist, out, per_sample}, B, stream);
 }
+#undef NIL
 
 // the start rule: out = hold_select(z, ...) with rows (k_x, k_n) = (sqrt(a_0), sqrt(1 - a_0)).  Every element is read, then written, by
 // the one thread that owns it (no __restrict__ on z / noise / out): out may alias z, and noise may be z itself.
