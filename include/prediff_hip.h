@@ -690,6 +690,32 @@ int pd_cdf_match(const float* x, const float* ref, int64_t lead, int64_t B, int 
                  int use_threshold, float* out, void* ws, int64_t ws_bytes, pd_stream_t stream);
 int pd_pmm(const float* ens, int M, int64_t frames, int H, int W, float* out, void* ws, int64_t ws_bytes, pd_stream_t stream);
 
+/* Distance-map verification (not in the reference; Gilleland 2011 / 2017; the definitions are the module docstring of
+ * prediff_amd/distance_score.py).  A frame is one (n, t) image of H x W fp32 pixels, C = 1, 1 <= H, W <= 128 (the maps of a frame live in
+ * LDS; else PD_ERR_ARG, the message names the limit), read in place.  Event set of a threshold: { s : v[s] / divisor >= thr } in fp32
+ * (IEEE division, as pd_sevir_skill_counts; divisor 1 compares the raw value; a NaN is never an event).  d2[s]: the squared Euclidean
+ * distance from pixel s to the nearest event of its frame, an exact integer <= 32258; 2^31 - 1 everywhere in a frame without events.
+ * pd_distance_map: sizes / strides: host int64[5] = N, T, H, W, C sizes and element strides (no negative stride) -> d2, device int32
+ *   (N, T, H, W), which must not alias the frames.
+ * pd_distance_update: pred holds M members of target's shape (1 <= M <= 512; pred_strides: host int64[6] = member, N, T, H, W, C;
+ *   target_strides: host int64[5]); thresholds: HOST float[K], 1 <= K <= 8.  Every frame is read once for all K thresholds and the target's
+ *   maps are made once for all members.  Per (member, n, t) pair, threshold k and step t (t = 0 unless keep_seq), with F / O the event sets
+ *   of pred / target and d = sqrt(double(d2)): a pair with a non-finite pixel in either frame adds 1 to counts[1][k][t] and nothing else;
+ *   every other pair adds 1 to counts[0][k][t], |F| to counts[4][k][t] and |O| to counts[5][k][t]; where F and O are both non-empty, 1 to
+ *   counts[2][k][t], mean over O of d_F to sums[0][k][t], mean over F of d_O to sums[1][k][t] and
+ *   sqrt(max(max over O of d2_F, max over F of d2_O)) (the maximum of integers) to sums[2][k][t]; Baddeley's
+ *   sqrt(sum over all pixels of (w(d_F) - w(d_O))^2 / (H W)) to sums[3][k][t] and 1 to counts[3][k][t], with w(d) = min(d, cutoff) and w = cutoff
+ *   for an empty set when use_cutoff != 0 (cutoff positive and finite; defined for every such pair), else w(d) = d where F and O are both
+ *   non-empty.  sums: device fp64 [4][K][T'], counts: device int64 [6][K][T'].  All sums are fp64, added in a fixed order, with no atomics: the
+ *   same inputs give the same bits.  ws: device workspace of pd_distance_ws_bytes(M, K, sizes) bytes (host-only; -1: unsupported M / K /
+ *   sizes), 16-byte aligned, aliasing neither an input nor the state. */
+int64_t pd_distance_ws_bytes(int M, int K, const int64_t* sizes);
+int pd_distance_map(const float* frames, const int64_t* sizes, const int64_t* strides, float threshold, float divisor, int* d2,
+                    pd_stream_t stream);
+int pd_distance_update(const float* pred, const float* target, int M, const int64_t* sizes, const int64_t* pred_strides,
+                       const int64_t* target_strides, const float* thresholds, int K, float divisor, int use_cutoff, double cutoff,
+                       int keep_seq, double* sums, long long* counts, void* ws, int64_t ws_bytes, pd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Fréchet video distance (evaluation/fvd/): the pieces of the I3D feature engine that are not pd_igemm, and the feature moments.
  * ------------------------------------------------------------------------------------------------- */

@@ -18,7 +18,8 @@ from .i3d import InceptionI3d  # noqa: E402,F401
 from .fvd import FrechetVideoDistance  # noqa: E402,F401
 from .spectrum import SEVIRSpectralScore  # noqa: E402,F401
 from .object_score import SEVIRObjectScore, label_objects  # noqa: E402,F401
-from .extrapolation import LagrangianPersistence  # noqa: E402,F401
+from .distance_score import SEVIRDistanceScore, distance_map  # noqa: E402,F401
+from .extrapolation import LagrangianPersistence # noqa: E402,F401
 from .steps import StochasticExtrapolation, steps_bands  # noqa: E402,F401
 from .anvil import AutoregressiveExtrapolation  # noqa: E402,F401
 from .probability_matching import match_cdf, probability_matched_mean, rank_frames  # noqa: E402,F401
