@@ -716,6 +716,27 @@ int pd_distance_update(const float* pred, const float* target, int M, const int6
                        const int64_t* target_strides, const float* thresholds, int K, float divisor, int use_cutoff, double cutoff,
                        int keep_seq, double* sums, long long* counts, void* ws, int64_t ws_bytes, pd_stream_t stream);
 
+/* Intensity-scale verification (not in the reference; Casati, Ross and Stephenson 2004; Casati 2010; the definitions are the module
+ * docstring of prediff_amd/scale_score.py).  Frames, event sets and limits are those of the distance block above (C = 1, 1 <= H, W <= 128,
+ * no negative stride, read in place; a NaN is never an event).  The 0 / 1 event field of a frame sits at the top-left corner of an S x S
+ * field of zeros, S = 2^n the smallest power of two >= max(H, W, 2) (n = 1 .. 7).  Q_l(A), l = 0 .. n: the sum over the 2^l x 2^l blocks
+ * of that field of (block sum of A)^2, an exact integer <= 4^(n + l) <= 2^28.  Everything after the event test is integer arithmetic.
+ * pd_scale_energy: sizes / strides: host int64[5] -> q_out, device int64 [N T][8]: Q_l of the event field of every frame at one
+ *   threshold, zero for l > n; q_out must not alias the frames.
+ * pd_scale_update: operands as pd_distance_update (thresholds: HOST float[K], 1 <= K <= 8; 1 <= M <= 512).  Every frame is read once for
+ *   all K thresholds and the target's event planes are made once for all members.  With I_F / I_O the event fields of pred / target and
+ *   Z = I_F - I_O, per (member, n, t) pair and step t (t = 0 unless keep_seq): a pair with a non-finite pixel in either frame adds 1 to
+ *   counts[1][t] and nothing else; every other pair adds 1 to counts[0][t] and Q_l(I_F), Q_l(I_O), Q_l(Z) to energy[0 / 1 / 2][k][l][t] for
+ *   l = 0 .. n (levels above n are not touched).  energy: device int64 [3][K][8][T'], counts: device int64 [2][T'].  No atomics; integer
+ *   sums in a fixed order.  ws: device workspace of pd_scale_ws_bytes(M, K, sizes) bytes (host-only; -1: unsupported M / K / sizes),
+ *   16-byte aligned, aliasing neither an input nor the state. */
+int64_t pd_scale_ws_bytes(int M, int K, const int64_t* sizes);
+int pd_scale_energy(const float* frames, const int64_t* sizes, const int64_t* strides, float threshold, float divisor, long long* q_out,
+                    pd_stream_t stream);
+int pd_scale_update(const float* pred, const float* target, int M, const int64_t* sizes, const int64_t* pred_strides,
+                    const int64_t* target_strides, const float* thresholds, int K, float divisor, int keep_seq, long long* energy,
+                    long long* counts, void* ws, int64_t ws_bytes, pd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Fréchet video distance (evaluation/fvd/): the pieces of the I3D feature engine that are not pd_igemm, and the feature moments.
  * ------------------------------------------------------------------------------------------------- */

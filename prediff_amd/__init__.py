@@ -19,6 +19,7 @@ from .fvd import FrechetVideoDistance  # noqa: E402,F401
 from .spectrum import SEVIRSpectralScore  # noqa: E402,F401
 from .object_score import SEVIRObjectScore, label_objects  # noqa: E402,F401
 from .distance_score import SEVIRDistanceScore, distance_map  # noqa: E402,F401
+from .scale_score import SEVIRScaleScore, scale_energy  # noqa: E402,F401
 from .extrapolation import LagrangianPersistence # noqa: E402,F401
 from .steps import StochasticExtrapolation, steps_bands  # noqa: E402,F401
 from .anvil import AutoregressiveExtrapolation  # noqa: E402,F401

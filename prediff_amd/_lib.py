@@ -212,6 +212,10 @@ _PROTOS = {
     "pd_distance_map": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "pd_distance_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_int, C.c_double, C.c_int]
                            + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "pd_scale_ws_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_void_p]),
+    "pd_scale_energy": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "pd_scale_update": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 3
+                        + [C.c_int64, C.c_void_p]),
     "pd_i3d_preprocess": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_maxpool3d_same": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.POINTER(CallOpts), C.c_void_p]),
     "pd_i3d_head": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
@@ -984,6 +988,27 @@ def distance_update(pred, target, M, sizes, pred_strides, target_strides, thresh
                                     len(thresholds), float(divisor), 0 if cutoff is None else 1, 0.0 if cutoff is None else float(cutoff),
                                     1 if keep_seq else 0, ptr(sums), ptr(counts), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
            "pd_distance_update")
+
+
+def scale_ws_bytes(M, K, sizes):
+    """pd_scale_ws_bytes: the workspace of scale_update; -1 for an unsupported M / K / shape (host-only)."""
+    return int(lib().pd_scale_ws_bytes(int(M), int(K), _i64(sizes)))
+
+
+def scale_energy(frames, sizes, strides, threshold, divisor, q_out):
+    """frames: fp32, read in place through the (N, T, H, W, C) sizes / strides; event: frames / divisor >= threshold in fp32; q_out: int64
+    (N T, 8), Q_l of every frame's event field, zero above the frame's top level."""
+    _check(lib().pd_scale_energy(ptr(frames), _i64(sizes), _i64(strides), float(threshold), float(divisor), ptr(q_out), stream_ptr()),
+           "pd_scale_energy")
+
+
+def scale_update(pred, target, M, sizes, pred_strides, target_strides, thresholds, divisor, keep_seq, energy, counts, ws):
+    """pred_strides: member stride followed by the (N, T, H, W, C) strides; thresholds: a host sequence of K numbers; energy int64
+    [3, K, 8, T'], counts int64 [2, T']; ws: a device tensor of at least scale_ws_bytes(M, K, sizes) bytes."""
+    thr = (C.c_float * len(thresholds))(*[float(t) for t in thresholds])
+    _check(lib().pd_scale_update(ptr(pred), ptr(target), int(M), _i64(sizes), _i64(pred_strides), _i64(target_strides), thr,
+                                 len(thresholds), float(divisor), 1 if keep_seq else 0, ptr(energy), ptr(counts), ptr(ws),
+                                 ws.numel() * ws.element_size(), stream_ptr()), "pd_scale_update")
 
 
 PM_RANK, PM_CDF, PM_PMM = 0, 1, 2                       # the ops of pd_pm_ws_bytes

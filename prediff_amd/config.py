@@ -125,7 +125,7 @@ def split_sequence(seq: torch.Tensor, in_len: int, out_len: int):
 def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int = 0, rank: int = 0, npy_dir: Optional[str] = None,
                      score=None, aligned_score=None, ensemble_score=None, aligned_ensemble_score=None, frame_score=None,
                      aligned_frame_score=None, object_score=None, aligned_object_score=None, distance_score=None,
-                     aligned_distance_score=None, **sample_kwargs):
+                     aligned_distance_score=None, scale_score=None, aligned_scale_score=None, **sample_kwargs):
     """The sampling part of test_step (train_sevirlr_prediff.py:905-979) for one batch of sequences (B, in_len+out_len, H, W, C).
 
     ensemble_score / aligned_ensemble_score (ensemble_score.SEVIREnsembleScore, layout of the sequences; not in the reference): after the
@@ -136,6 +136,8 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
     every sample where frame_score / aligned_frame_score are.
     distance_score / aligned_distance_score (distance_score.SEVIRDistanceScore: mean error distances, Hausdorff, Baddeley's Delta; not in
     the reference): updated with every sample where object_score / aligned_object_score are.
+    scale_score / aligned_scale_score (scale_score.SEVIRScaleScore: the intensity-scale skill score and the Haar energies; not in the
+    reference): updated with every sample where distance_score / aligned_distance_score are.
     **sample_kwargs go to ldm.sample unchanged: sampler="ddim", ddim_steps=..., eta=... or sampler="dpmpp_2m", steps=..., discretize=...,
     lower_order_final=..., noise_tape=... or sampler="dpmpp_2m_sde", steps=..., eta=... (both branches run the sampler they name)."""
     import numpy as np
@@ -159,6 +161,8 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
                 aligned_object_score.update(pred.float(), tgt)
             if aligned_distance_score is not None:
                 aligned_distance_score.update(pred.float(), tgt)
+            if aligned_scale_score is not None:
+                aligned_scale_score.update(pred.float(), tgt)
             out["aligned_pred"].append(pred)
         if ev.get("eval_unaligned", True):
             pred = ldm.sample(cond={"y": ctx}, batch_size=B, **sample_kwargs).contiguous()
@@ -172,6 +176,8 @@ def evaluate_context(ldm, seq: torch.Tensor, cfg: Dict[str, Any], batch_idx: int
                 object_score.update(pred.float(), tgt)
             if distance_score is not None:
                 distance_score.update(pred.float(), tgt)
+            if scale_score is not None:
+                scale_score.update(pred.float(), tgt)
             out["pred"].append(pred)
     if ensemble_score is not None and out["pred"]:
         ensemble_score.update(torch.stack(out["pred"]).float(), tgt)

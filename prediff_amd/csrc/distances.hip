@@ -292,23 +292,6 @@ int dm_check(const char* who, const int64_t* sizes, float divisor) {
   return PD_OK;
 }
 
-// bytes from `base` to the end of the last element that sizes / strides (n axes, no stride negative) address; -1: a negative stride
-int64_t dm_span(const int64_t* sizes, const int64_t* strides, int n, int64_t lead, int64_t s_lead) {
-  int64_t last = 0;
-  if (s_lead < 0) return -1;
-  last += (lead - 1) * s_lead;
-  for (int i = 0; i < n; ++i) {
-    if (strides[i] < 0) return -1;
-    last += (sizes[i] - 1) * strides[i];
-  }
-  return (last + 1) * (int64_t)sizeof(float);
-}
-
-bool dm_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const char *pa = (const char*)a, *pb = (const char*)b;
-  return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 int dm_launch(DmSource src, int64_t frames, const DmParams& q, int* d2, unsigned short* maps_out, const unsigned short* tmaps, int* info,
               double* rec, hipStream_t stream) {
   const int lds = (int)dm_lds_bytes(q.h, q.w);
@@ -332,9 +315,9 @@ extern "C" int pd_distance_map(const float* frames, const int64_t* sizes, const 
   if (int rc = dm_check("pd_distance_map", sizes, divisor)) return rc;
   const int64_t nf = dm_frames(0, sizes);
   PD_CHECK_ARG(nf > 0, "pd_distance_map: too many frames in one call");
-  const int64_t span = dm_span(sizes, strides, 4, 1, 0);
+  const int64_t span = axes_span(sizes, strides, 4, 1, 0);
   PD_CHECK_ARG(span > 0, "pd_distance_map: negative stride");
-  PD_CHECK_ARG(!dm_overlap(d2, nf * sizes[2] * sizes[3] * (int64_t)sizeof(int), frames, span), "pd_distance_map: d2 aliases the frames");
+  PD_CHECK_ARG(!bytes_overlap(d2, nf * sizes[2] * sizes[3] * (int64_t)sizeof(int), frames, span), "pd_distance_map: d2 aliases the frames");
   DmParams q = {};
   q.h = (int)sizes[2], q.w = (int)sizes[3], q.k = 1, q.n = sizes[0], q.t = sizes[1];
   q.divisor = divisor, q.thr[0] = threshold;
@@ -356,15 +339,15 @@ extern "C" int pd_distance_update(const float* pred, const float* target, int M,
   PD_CHECK_ARG(dm_ws(M, K, sizes, w), "pd_distance_update: too many frames in one update");
   PD_CHECK_ARG(ws_bytes >= w.bytes, "pd_distance_update: workspace of %lld bytes < %lld", (long long)ws_bytes, (long long)w.bytes);
   PD_CHECK_ARG(((uintptr_t)ws & 15) == 0, "pd_distance_update: the workspace is not 16-byte aligned");
-  const int64_t pspan = dm_span(sizes, pred_strides + 1, 4, M, pred_strides[0]), tspan = dm_span(sizes, target_strides, 4, 1, 0);
+  const int64_t pspan = axes_span(sizes, pred_strides + 1, 4, M, pred_strides[0]), tspan = axes_span(sizes, target_strides, 4, 1, 0);
   PD_CHECK_ARG(pspan > 0 && tspan > 0, "pd_distance_update: negative stride");
   const int64_t N = sizes[0], T = sizes[1], Tk = keep_seq ? T : 1;
   const int64_t sbytes = 4 * K * Tk * (int64_t)sizeof(double), cbytes = 6 * K * Tk * (int64_t)sizeof(long long);
-  PD_CHECK_ARG(!dm_overlap(ws, w.bytes, pred, pspan) && !dm_overlap(ws, w.bytes, target, tspan) && !dm_overlap(ws, w.bytes, sums, sbytes) &&
-                   !dm_overlap(ws, w.bytes, counts, cbytes),
+  PD_CHECK_ARG(!bytes_overlap(ws, w.bytes, pred, pspan) && !bytes_overlap(ws, w.bytes, target, tspan) && !bytes_overlap(ws, w.bytes, sums, sbytes) &&
+                   !bytes_overlap(ws, w.bytes, counts, cbytes),
                "pd_distance_update: the workspace aliases an input or the state");
-  PD_CHECK_ARG(!dm_overlap(sums, sbytes, pred, pspan) && !dm_overlap(sums, sbytes, target, tspan) && !dm_overlap(counts, cbytes, pred, pspan) &&
-                   !dm_overlap(counts, cbytes, target, tspan) && !dm_overlap(sums, sbytes, counts, cbytes),
+  PD_CHECK_ARG(!bytes_overlap(sums, sbytes, pred, pspan) && !bytes_overlap(sums, sbytes, target, tspan) && !bytes_overlap(counts, cbytes, pred, pspan) &&
+                   !bytes_overlap(counts, cbytes, target, tspan) && !bytes_overlap(sums, sbytes, counts, cbytes),
                "pd_distance_update: the state aliases an input");
   double* rec = (double*)((char*)ws + w.rec);
   int* info = (int*)((char*)ws + w.info);

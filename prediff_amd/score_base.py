@@ -1,5 +1,5 @@
-"""What the six SEVIR score classes share (``SEVIRSkillScore``, ``SEVIREnsembleScore``, ``SEVIRFrameScore``, ``SEVIRSpectralScore``,
-``SEVIRObjectScore``, ``SEVIRDistanceScore``):
+"""What the seven SEVIR score classes share (``SEVIRSkillScore``, ``SEVIREnsembleScore``, ``SEVIRFrameScore``, ``SEVIRSpectralScore``,
+``SEVIRObjectScore``, ``SEVIRDistanceScore``, ``SEVIRScaleScore``):
 the N, T, H, W, C view of a tensor in a layout, the constructor checks, the life cycle of the accumulated state and its ``sync``, the
 member-stack checks of ``update`` and the workspace.  A subclass declares its metrics, its state tensors and what its layout must
 name; ``update`` and ``compute`` are its own.
